@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on the BASELINE.json configurations, one MI355X per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}] [--full] [--dump-outputs DIR]
 
   --config 1 (default, the BASELINE metric): QPs/sec for one forward + one backward of the differentiable batched
       QP solver, batch 4096 per GPU, n_state 3, n_ctrl 3, T 5 (nz 30, nineq 30, neq 15; random dense family R of
@@ -20,11 +20,21 @@ call; the parent only waits and exits non-zero if a child fails.  No rank touche
 collectives are the single gather of the solved batch north_star names (configs 1-4) and the gradient all-reduce of
 config 5.  Timing: W warm-up steps, then exactly K steps between barrier + synchronize on both sides, MAX over ranks.
 
-Rank 0 prints ONE JSON line with `roofline` (the library kernel with the largest share of the step, timed live with
-HIP events on its launch stream by the library's own trace, dqp_trace_begin / dqp_trace_end; algorithmic bytes as
-DESIGN.md section 4 defines them per kernel) and `cpu_baseline` (the oracle -- a CPU port of the reference's
-algorithm -- timed on this host on a bounded sample of the same workload; N = 1 only).  The default run (config 1,
-one GPU) also appends `other_configs`: a short timed run of each of configs 2-5 (--no-other-configs skips them).
+Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one
+timed step) and the run's description.  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs
+(--dump-outputs) and the line.
+
+--full adds what takes runs of its own: `roofline` (the library kernel with the largest share of the step, timed live
+with HIP events on its launch stream by the library's own trace, dqp_trace_begin / dqp_trace_end; algorithmic bytes as
+DESIGN.md section 4 defines them per kernel), `kernels`, `kernels_extra`, and `cpu_baseline` (the oracle -- a CPU port
+of the reference's algorithm -- timed on this host on a bounded sample of the same workload; N = 1 only;
+--no-cpu-baseline skips it).  On config 1 with one GPU it also appends the other termination mode (`fast_mode`) and
+`other_configs`: a short timed run of each of configs 2-5 (--no-other-configs skips them).
+
+--dump-outputs DIR writes what the last timed step computed -- the arrays a caller of the timed path receives -- as
+DIR/<name>.npy in float64 (rank 0's shard), at most 64 MiB in all: above that, every batch-major array keeps the same
+fixed, seeded sample of batch rows.  Inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import ctypes
@@ -190,6 +200,10 @@ class Workload:
     def extras(self):
         return {}
 
+    def outputs(self):
+        """what the last step returned to its caller: ({name: batch-major tensor}, {name: other tensor})"""
+        return {}, {}
+
 
 def family_R(torch, seed, B, nz, nineq, neq):
     g = torch.Generator().manual_seed(seed)
@@ -298,6 +312,11 @@ class MetricQP(Workload):
         return {"pdipm_iters_mean": float(iters.mean()), "pdipm_iters_max": float(iters.max()),
                 "status_nonzero": int((self.info[:, 0] != 0).sum())}
 
+    def outputs(self):
+        # dqp_qp_forward's outputs (info: status, iterations) and dqp_qp_backward's gradients
+        names = ("zhat", "lam", "nu", "slack", "info", "resid", "dQ", "dp", "dG", "dh", "dA", "db")
+        return {k: getattr(self, k) for k in names}, {}
+
     def cpu_baseline(self, reps=3):
         """The oracle (a C port of the reference's algorithm, OpenMP over the batch) on this host."""
         import numpy as np
@@ -355,6 +374,7 @@ class PendulumMPC(Workload):
             x, u = self.graphed(self.x0, self.C, self.c)
         else:
             x, u = self.mpc(self.x0, self.qp_wrapper.QuadCost(self.C, self.c), self.dyn, self.dyn.jac)
+        self.x = x.detach()
         self.u = u.detach().transpose(0, 1).contiguous()
         work = gather(self.u) if gather else None
         self.C.grad = self.c.grad = None
@@ -381,6 +401,14 @@ class PendulumMPC(Workload):
 
     def extras(self):
         return {"max_abs_u": float(self.u.abs().max())}
+
+    def outputs(self):
+        # x, u of the call and the gradients of the step's loss w.r.t. the cost (time-major in qp_wrapper)
+        out = {"x": self.x.transpose(0, 1), "u": self.u}
+        for k, t in (("dC", self.C.grad), ("dc", self.c.grad)):
+            if t is not None:
+                out[k] = t.transpose(0, 1)
+        return out, {}
 
     def cpu_baseline(self):
         """DenseQPFunction (batch_LU.py) forward + backward of the assembled QP of this call, C oracle, OpenMP."""
@@ -482,6 +510,13 @@ class RobotAL(Workload):
                - xs[:, 1:]).abs().amax(dim=(1, 2))
         return {"dynamics_gap_median": float(gap.median()), "dynamics_gap_max": float(gap.max()),
                 "finite": bool(torch.isfinite(xs).all())}
+
+    def outputs(self):
+        out = {"x": self.x, "u": self.u}
+        for k, t in (("dC", self.C.grad), ("dc", self.c.grad)):
+            if t is not None:
+                out[k] = t
+        return out, {}
 
     def cpu_baseline(self, budget_s=12.0):
         """oracle/al_solve_oracle.py (numpy port of AL_mpc.MPC.al_solve + NewtonAL.backward), one thread."""
@@ -632,6 +667,11 @@ class DEQMPCTrain(Workload):
     def extras(self):
         return {"loss": float(self.loss)}
 
+    def outputs(self):
+        # the step's loss and the model it leaves behind (the parameters after the optimiser step, flattened)
+        params = self.torch.cat([p.detach().reshape(-1).double() for p in self.policy.model.parameters()])
+        return {}, {"loss": self.loss.reshape(1), "params": params}
+
     def cpu_baseline(self, budget_s=12.0):
         torch = self.torch
         f64 = dict(dtype=torch.float64, device=self.x.device)
@@ -646,6 +686,33 @@ class DEQMPCTrain(Workload):
         return out
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(torch, wl, out_dir):
+    """--dump-outputs: wl.outputs() as out_dir/<name>.npy, float64.  When the whole would exceed DUMP_LIMIT_BYTES, every
+    batch-major array keeps the same rows: a sample drawn with a fixed seed, in batch order (the same rows on every run
+    of the same configuration).  Returns the number of batch rows written."""
+    import numpy as np
+    batched, other = wl.outputs()
+    fixed = sum(t.numel() * 8 for t in other.values()) + 256 * (len(batched) + len(other))     # + .npy headers
+    per_row = sum(t[0].numel() * 8 for t in batched.values())
+    B = next(iter(batched.values())).shape[0] if batched else 0
+    assert all(t.shape[0] == B for t in batched.values()), {k: tuple(t.shape) for k, t in batched.items()}
+    rows = B if per_row == 0 else min(B, (DUMP_LIMIT_BYTES - fixed) // per_row)
+    idx = None
+    if rows < B:
+        pick = np.sort(np.random.default_rng(0).choice(B, rows, replace=False))
+        idx = torch.from_numpy(pick)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in list(batched.items()) + list(other.items()):
+        t = t.detach()
+        if idx is not None and name in batched:
+            t = t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64).cpu().numpy())
+    return rows
+
+
 WORKLOADS = {1: MetricQP, 2: PendulumMPC, 3: CartpoleAL, 4: QuadrotorAL, 5: DEQMPCTrain}
 DEFAULT_STEPS = {1: (200, 10), 2: (50, 5), 3: (30, 3), 4: (10, 2), 5: (5, 2)}
 
@@ -658,9 +725,14 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", type=int, default=1, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel trace and roofline, the CPU baseline and (config 1, one GPU) the other "
+                         "termination mode and configs 2-5: each takes runs of its own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (config 1, one GPU): do not append the short runs of configs 2-5 (`other_configs`)")
+                    help="--full run (config 1, one GPU): do not append the short runs of configs 2-5 (`other_configs`)")
     ap.add_argument("--batch", type=int, default=None, help="configs 3 and 5: another batch size (per GPU for 3, global for 5)")
     ap.add_argument("--robot", default=None, help="config 3: another registered model (cartpole2l, pendulum_euler, ...)")
     ap.add_argument("--T", type=int, default=None, help="config 3: another horizon")
@@ -672,6 +744,8 @@ def main(argv=None):
         args.steps = DEFAULT_STEPS[args.config][0]
     if args.warmup is None:
         args.warmup = DEFAULT_STEPS[args.config][1]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:       # no launcher around us: start the ranks ourselves, before any GPU call
@@ -753,52 +827,58 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # per-kernel times of the same step, HIP events on the launch stream (the library's own trace)
-    tsteps = max(1, min(args.steps, 20))
-    graphed, wl.graphed = getattr(wl, "graphed", None), None       # graph replays launch nothing through the library: trace the eager step
-    with _lib.trace(20000) as tr:          # (a step is at most ~150 library launches; the event pool is per slot)
-        for _ in range(tsteps):
-            wl.step(None)
-        torch.cuda.synchronize()
-    wl.graphed = graphed
-    kern = {short_kernel(k): (c / tsteps, ms) for k, (c, ms) in tr.by_kernel().items()}
-    total_kernel_ms = sum(c * ms for c, ms in kern.values())
-
     out = None
     if rank == 0:
-        value = world * wl.units * args.steps / elapsed
-        dom = max(kern, key=lambda k: kern[k][0] * kern[k][1])
-        dom_launches, dom_ms = kern[dom]
-        dom_bytes = wl.kernel_bytes(dom)
-        pm = pmc_summary(args.config)
-        kpm = next((v for k, v in pm.items() if isinstance(v, dict) and short_kernel(k) == dom), {})
-        gbs = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None
         out = {
-            "metric": wl.metric, "value": value, "unit": wl.unit, "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "metric": wl.metric, "value": world * wl.units * args.steps / elapsed, "unit": wl.unit, "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": wl.scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic", "config": dict(wl.describe(world), baseline_config=args.config),
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": gbs / HBM_PEAK_GBS if gbs else None, "traffic": traffic_of(kpm),
-                         "traffic_source": ("profiles/r3/pmc_config%d.json (rocprofv3 --pmc passes of this command on "
-                                            "these kernel sources)" % args.config if traffic_of(kpm) is not None else None),
-                         "avg_launch_ms": dom_ms, "launches_per_step": dom_launches,
-                         "share_of_step_kernel_time": dom_launches * dom_ms / total_kernel_ms if total_kernel_ms else None,
-                         "algorithmic_bytes_per_launch": dom_bytes,
-                         "note": "dominant library kernel of the step by total time, HIP events on the launch stream "
-                                 "(dqp_trace_*); these kernels are fp64-issue / latency bound, not HBM bound (DESIGN.md "
-                                 "section 4) -- see `fp64` for the executed-instruction rate"},
-            "kernels": {k: {"launches_per_step": round(c, 2), "avg_ms": ms,
-                            "GBps": (wl.kernel_bytes(k) / (ms * 1e-3) / 1e9 if wl.kernel_bytes(k) else None)}
-                        for k, (c, ms) in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])[:8]},
-            "kernel_ms_per_step": total_kernel_ms,
         }
-        out["kernels_extra"] = wl.extras()
-        f64 = fp64_of(kpm, dom_ms) if kpm else None
-        if f64:
-            out["fp64"] = f64
+        if args.dump_outputs:           # before anything else runs the workload again
+            dump_outputs(torch, wl, args.dump_outputs)
 
-    if args.config == 1 and world == 1:       # the other termination mode, same inputs
+    if args.full:
+        # per-kernel times of the same step, HIP events on the launch stream (the library's own trace)
+        tsteps = max(1, min(args.steps, 20))
+        graphed, wl.graphed = getattr(wl, "graphed", None), None       # graph replays launch nothing through the library: trace the eager step
+        with _lib.trace(20000) as tr:          # (a step is at most ~150 library launches; the event pool is per slot)
+            for _ in range(tsteps):
+                wl.step(None)
+            torch.cuda.synchronize()
+        wl.graphed = graphed
+        kern = {short_kernel(k): (c / tsteps, ms) for k, (c, ms) in tr.by_kernel().items()}
+        total_kernel_ms = sum(c * ms for c, ms in kern.values())
+
+        if rank == 0:
+            dom = max(kern, key=lambda k: kern[k][0] * kern[k][1])
+            dom_launches, dom_ms = kern[dom]
+            dom_bytes = wl.kernel_bytes(dom)
+            pm = pmc_summary(args.config)
+            kpm = next((v for k, v in pm.items() if isinstance(v, dict) and short_kernel(k) == dom), {})
+            gbs = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_bytes else None
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": gbs / HBM_PEAK_GBS if gbs else None, "traffic": traffic_of(kpm),
+                             "traffic_source": ("profiles/r3/pmc_config%d.json (rocprofv3 --pmc passes of this command on "
+                                                "these kernel sources)" % args.config if traffic_of(kpm) is not None else None),
+                             "avg_launch_ms": dom_ms, "launches_per_step": dom_launches,
+                             "share_of_step_kernel_time": dom_launches * dom_ms / total_kernel_ms if total_kernel_ms else None,
+                             "algorithmic_bytes_per_launch": dom_bytes,
+                             "note": "dominant library kernel of the step by total time, HIP events on the launch stream "
+                                     "(dqp_trace_*); these kernels are fp64-issue / latency bound, not HBM bound (DESIGN.md "
+                                     "section 4) -- see `fp64` for the executed-instruction rate"},
+                "kernels": {k: {"launches_per_step": round(c, 2), "avg_ms": ms,
+                                "GBps": (wl.kernel_bytes(k) / (ms * 1e-3) / 1e9 if wl.kernel_bytes(k) else None)}
+                            for k, (c, ms) in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])[:8]},
+                "kernel_ms_per_step": total_kernel_ms,
+            })
+            out["kernels_extra"] = wl.extras()
+            f64 = fp64_of(kpm, dom_ms) if kpm else None
+            if f64:
+                out["fp64"] = f64
+
+    if args.full and args.config == 1 and world == 1:       # the other termination mode, same inputs
         other = "per_problem" if wl.termination == "batch" else "batch"
         zhat_head = wl.zhat.clone()
         wl2 = MetricQP(torch, dev, rank, world, args, termination=other)
@@ -816,10 +896,10 @@ def main(argv=None):
             "max_abs_dzhat_vs_headline": float((wl2.zhat - zhat_head).abs().max()),
             "note": "float-tolerance parity only (include/dqp.h); every problem stops on its own"}
 
-    if args.config == 1 and world == 1 and not args.no_other_configs and args.batch is None:
+    if args.full and args.config == 1 and world == 1 and not args.no_other_configs and args.batch is None:
         # the other BASELINE configurations, each a short timed run of the same kind (warm-up, K steps between
-        # synchronisations, the library's trace for the dominant kernel): in the default line so that whoever runs
-        # `python bench.py` has all five on record; `--config C` gives a configuration its full line
+        # synchronisations, the library's trace for the dominant kernel): in the --full line so that whoever runs
+        # `python bench.py --full` has all five on record; `--config C` gives a configuration its own line
         out["other_configs"] = {}
         for c in (2, 3, 4, 5):
             try:
@@ -852,7 +932,7 @@ def main(argv=None):
                 out["other_configs"][str(c)] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:     # the CPU baseline is an N=1, rank-0 figure
+        if args.full and not args.no_cpu_baseline and world == 1:     # the CPU baseline is an N=1, rank-0 figure
             cb = wl.cpu_baseline()
             if cb:
                 out["cpu_baseline"] = cb

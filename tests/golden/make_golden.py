@@ -185,6 +185,11 @@ def save(name, d_in, outs):
     arrs.update(outs)
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **arrs)
+    if os.path.getsize(path) > 1 << 20:     # committed files stay under 1 MiB: the gradients go to more/<name>.npz
+        grads = {k: v for k, v in arrs.items() if k.startswith(("dQ_", "dp_", "dG_", "dh_", "dA_", "db_"))}
+        os.makedirs(os.path.join(HERE, "more"), exist_ok=True)
+        np.savez_compressed(os.path.join(HERE, "more", name + ".npz"), **grads)
+        np.savez_compressed(path, **{k: v for k, v in arrs.items() if k not in grads})
     print("wrote %-28s %6.1f KB  zhat[0,:3]=%s" % (
         name + ".npz", os.path.getsize(path) / 1024, np.array2string(
             arrs.get("zhat", arrs.get("x", np.zeros((1, 3))))[0].ravel()[:3], precision=6)))

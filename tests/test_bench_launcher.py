@@ -39,3 +39,34 @@ def test_child_failure_fails_the_parent():
 def test_world_size_mismatch_is_an_error():
     r = run(["--gpus", "4"], WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
+
+
+def test_dump_outputs_writes_float64_within_the_cap_on_a_fixed_sample(tmp_path):
+    """--dump-outputs on a CPU stand-in workload over the 64 MiB cap: every batch-major array keeps the same rows
+    (a seeded sample, in batch order), other arrays are written whole, and two runs write identical files."""
+    import numpy as np
+    import torch
+    import bench
+
+    B = 4096
+
+    class Stub:
+        def outputs(self):
+            row = torch.arange(B, dtype=torch.int32)
+            big = row[:, None].double().repeat(1, 2100)                  # 68.8 MB alone
+            return {"row": row, "big": big}, {"loss": torch.tensor([0.5], dtype=torch.float32)}
+
+    rows = []
+    for d in ("a", "b"):
+        rows.append(bench.dump_outputs(torch, Stub(), str(tmp_path / d)))
+    assert rows[0] == rows[1] < B
+    total = 0
+    for name in ("row", "big", "loss"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    row, big = np.load(tmp_path / "a" / "row.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert row.shape == (rows[0],) and big.shape == (rows[0], 2100)
+    assert np.all(np.diff(row) > 0) and np.array_equal(big[:, 0], row) and np.array_equal(big[:, -1], row)
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.5]

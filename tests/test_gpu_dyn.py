@@ -1,8 +1,9 @@
 """GPU parity of the device dynamics registry (include/dqp.h dqp_dyn_*) against
 the golden vectors of tests/golden/DYN_*.npz (the reference's CasADi-generated C for the robots,
-its torch modules for the pendulums; make_golden_dyn.py) and, when oracle/_ref travelled to the box,
-against the reference's compiled C on fresh random states.  Tolerances (absolute, values O(1-10)):
+its torch modules for the pendulums; make_golden_dyn.py) and against the reference's compiled C on 4000 of the
+random states of a full-size call (tests/golden/DYNFULL_*.npz, make_golden_dynfull.py).  Tolerances (absolute, values O(1-10)):
 states 1e-12, Jacobians 1e-11."""
+import glob
 import os
 
 import numpy as np
@@ -57,9 +58,8 @@ def test_extension_interface_vs_golden(dynmod, name):
 
 @pytest.mark.parametrize("name", NAMES[:3])
 def test_vs_compiled_reference_full_size(dynmod, name):
-    """B x (T-1) = 4096 x 19 knots (the config-3 Jacobian call): every sample against oracle/_ref."""
-    if not dyn_ref.available(name):
-        pytest.skip("oracle/_ref did not travel")
+    """B x (T-1) = 4096 x 19 knots (the config-3 Jacobian call): 4000 sampled knots against the reference's compiled C
+    (its outputs on exactly these states, stored by tests/golden/make_golden_dynfull.py)."""
     nq = dyn_ref.ROBOTS[name]
     N = 4096 * 19
     rng = np.random.default_rng(5)
@@ -67,9 +67,13 @@ def test_vs_compiled_reference_full_size(dynmod, name):
     u = rng.uniform(-100, 100, (N, 1))
     dyn = dynmod.DeviceDynamics(name, dt=0.05)
     xn, (Jx, Ju) = dyn.jac(dev(x), dev(u))
-    sub = rng.choice(N, 4000, replace=False)            # the ctypes reference is per-sample Python
-    ref = dyn_ref.step_x(name, x[sub], u[sub], 0.05)
-    rJx, rJu = dyn_ref.jac_x(name, x[sub], u[sub], 0.05)
+    sub = rng.choice(N, 4000, replace=False)            # the knots the reference's outputs are stored for
+    parts = [np.load(p) for p in sorted(glob.glob(os.path.join(GOLDEN, "DYNFULL_%s_*.npz" % name)))]
+    g = {k: np.concatenate([p[k] for p in parts]) for k in ("sub", "x", "u", "x_next", "Jx", "Ju")}
+    np.testing.assert_array_equal(g["sub"], sub)       # the same states as the stored reference outputs
+    np.testing.assert_array_equal(g["x"], x[sub])
+    np.testing.assert_array_equal(g["u"], u[sub])
+    ref, rJx, rJu = g["x_next"], g["Jx"], g["Ju"]
     scale = 1.0 + np.abs(ref).max()
     np.testing.assert_allclose(xn.cpu().numpy()[sub], ref, rtol=0, atol=1e-12 * scale)
     np.testing.assert_allclose(Jx.cpu().numpy()[sub], rJx, rtol=1e-10, atol=1e-10)

@@ -4,7 +4,7 @@
 for rep in 1 2; do
 for n in "$@"; do
   if [ "$n" = main ]; then unset DQP_HIP_LIBRARY; else export DQP_HIP_LIBRARY=$PWD/diff-qp-mpc_amd/csrc/libdqp_hip_ab_$n.so; fi
-  python bench.py --config 1 --no-cpu-baseline --steps 300 --warmup 20 2>/dev/null | python -c "
+  python bench.py --config 1 --full --no-cpu-baseline --steps 300 --warmup 20 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']; f=[v for kk,v in k.items() if 'forward_kernel' in kk][0]; b=[v for kk,v in k.items() if 'backward_kernel' in kk][0]
