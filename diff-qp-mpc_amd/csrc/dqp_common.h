@@ -116,6 +116,15 @@ int ric_forward_stepped(const KParams &P, void *stream);   // iterations [P.itBe
 int ric_backward(const KParams &P, void *stream);
 int ric_snapshot_doubles(int n_state, int n_ctrl, int T);   // iterate snapshot of the batch rule's finish pass
 int ric_finish(const KParams &P, void *stream);
+// the same kernels for 16 < n + m <= 32 (dqp_ric_wide.hip): one QP per 32-lane half-wavefront, the per-QP
+// workspace layout and the snapshot of the 16-lane form (ric_finish serves both), workspaces padded to an even B
+bool ricw_supported(int n_state, int n_ctrl);
+long long ricw_workspace_doubles(int n_state, int n_ctrl, int T);
+int ricw_forward(const KParams &P, void *stream);     // 1: no kernel for this (n, m) or a dynamics model
+long long ricw_stepped_workspace_doubles(int n_state, int n_ctrl, int T, int B);
+int ricw_forward_stepped(const KParams &P, void *stream);
+int ricw_backward(const KParams &P, void *stream);
+int ricw_snapshot_doubles(int n_state, int n_ctrl, int T);
 // dense QPs above DQP_MAX_DIM (dqp_big.hip): one QP per workgroup, matrices in the workspace, MFMA tiles
 long long big_workspace_doubles(int N, int M, int E);
 bool big_fits(int N, int M, int E);         // the solver's vectors fit the LDS of a CU

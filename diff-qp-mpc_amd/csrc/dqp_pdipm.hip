@@ -904,8 +904,14 @@ static int forward_once(const KParams &P, size_t lds, void *workspace, void *str
 // time-major MPC data and scatter the gradients back the same way -- no dense QP in HBM.
 // Which kernels serve an MPC shape: the dense null-space kernels where the QP size has an
 // instantiation (small horizons: one QP in registers), else the stage-wise Riccati kernels
-// (dqp_ric.hip: any horizon, n + m <= 16).
-enum { MPC_NONE = 0, MPC_R16N = 1, MPC_RIC = 2 };
+// (dqp_ric.hip: any horizon, n + m <= 16; dqp_ric_wide.hip: the same for 16 < n + m <= 32).
+enum { MPC_NONE = 0, MPC_R16N = 1, MPC_RIC = 2, MPC_RICW = 3 };
+
+// per-QP workspace of the stage-wise kernels (the same layout in both families); 0: no kernel for (n, m)
+static long long stage_ws_doubles(int n, int m, int T)
+{
+    return ric_supported(n, m) ? ric_workspace_doubles(n, m, T) : ricw_workspace_doubles(n, m, T);
+}
 
 static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, size_t &lds, int &kind)
 {
@@ -927,15 +933,15 @@ static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, 
         int rc = fill_params(&d, opts ? &o2 : nullptr, P, lds);
         if (rc != DQP_OK) return rc;
         kind = MPC_R16N;
-    } else if (ric_supported(md->n_state, md->n_ctrl)) {
+    } else if (ric_supported(md->n_state, md->n_ctrl) || ricw_supported(md->n_state, md->n_ctrl)) {
         // the stage-wise kernels address a wavefront's four workspaces with 32-bit byte offsets
-        if (md->T > 200000 || ric_workspace_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
+        if (md->T > 200000 || stage_ws_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
         P.stamps = nullptr;
         P.B = d.nbatch; P.N = d.nz; P.M = d.nineq; P.E = d.neq;
         fill_opts(opts, P);
         P.dynId = md->dyn_id;
         P.dynDt = opts ? opts->dyn_dt : 0.0;
-        kind = MPC_RIC;
+        kind = ric_supported(md->n_state, md->n_ctrl) ? MPC_RIC : MPC_RICW;
     } else {
         return DQP_ERR_TOO_LARGE;
     }
@@ -946,12 +952,14 @@ static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, 
 static size_t mpc_workspace_doubles(const KParams &P, int kind)
 {
     if (kind == MPC_R16N) return (size_t)P.B * (size_t)r16n_workspace_doubles(P.N, P.M, P.E);
-    // four problems per wavefront, padding rows own a slot too
+    // four problems per wavefront (two for the wide pairs), padding rows own a slot too
+    if (kind == MPC_RICW) return (size_t)((P.B + 1) / 2 * 2) * (size_t)ricw_workspace_doubles(P.mn, P.mm, P.mT);
     return (size_t)((P.B + 3) / 4 * 4) * (size_t)ric_workspace_doubles(P.mn, P.mm, P.mT);
 }
 
 static int mpc_snapshot_doubles(const KParams &P, int kind)
 {
+    if (kind == MPC_RICW) return ricw_snapshot_doubles(P.mn, P.mm, P.mT);
     return kind == MPC_R16N ? r16n_snapshot_doubles(P.N, P.M, P.E) : ric_snapshot_doubles(P.mn, P.mm, P.mT);
 }
 
@@ -996,7 +1004,9 @@ dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C
     if (!C || !c || !F || !f || !x0 || !u_lower || !u_upper || !tau || !lam || !nu || !slack || !workspace)
         return DQP_ERR_BAD_ARG;
     if (P.dynId && !(P.dynDt > 0.0)) return DQP_ERR_BAD_ARG;        // the model's step needs dqp_opts.dyn_dt
-    auto run = [&](const KParams &Q) { return kind == MPC_R16N ? r16n_forward(Q, stream) : ric_forward(Q, stream); };
+    auto run = [&](const KParams &Q) {
+        return kind == MPC_R16N ? r16n_forward(Q, stream) : kind == MPC_RICW ? ricw_forward(Q, stream) : ric_forward(Q, stream);
+    };
     P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0; P.mul = u_lower; P.muu = u_upper;
     P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
     P.workspace = (double *)workspace;
@@ -1012,12 +1022,17 @@ dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C
     return kind == MPC_R16N ? r16n_forward(P, stream) : ric_finish(P, stream);
 }
 
+static int stage_snapshot_doubles(int n, int m, int T)
+{
+    return ric_supported(n, m) ? ric_snapshot_doubles(n, m, T) : ricw_snapshot_doubles(n, m, T);
+}
+
 // the stage-wise kernels only, whatever the horizon (the null-space kernels keep their iterate in registers)
 static int stepped_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P)
 {
     if (!md || md->nbatch < 0 || md->n_state <= 0 || md->n_ctrl <= 0 || md->T < 2 || !md->has_bounds) return DQP_ERR_BAD_ARG;
-    if (!ric_supported(md->n_state, md->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    if (md->T > 200000 || ric_workspace_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
+    if (!ric_supported(md->n_state, md->n_ctrl) && !ricw_supported(md->n_state, md->n_ctrl)) return DQP_ERR_TOO_LARGE;
+    if (md->T > 200000 || stage_ws_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
     P.B = md->nbatch;
     P.N = md->T * (md->n_state + md->n_ctrl); P.M = 2 * md->T * md->n_ctrl; P.E = md->T * md->n_state;
     fill_opts(opts, P);
@@ -1029,14 +1044,16 @@ __attribute__((visibility("default"))) size_t dqp_mpc_qp_stepped_workspace_bytes
 {
     KParams P = {};
     if (stepped_params(md, nullptr, P) != DQP_OK || md->nbatch <= 0) return 0;
-    return (size_t)ric_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B) * sizeof(double);
+    const long long n = ric_supported(P.mn, P.mm) ? ric_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B)
+                                                  : ricw_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B);
+    return (size_t)n * sizeof(double);
 }
 
 __attribute__((visibility("default"))) size_t dqp_mpc_qp_stepped_termination_bytes(const dqp_mpc_dims *md, const dqp_opts *o)
 {
     KParams P = {};
     if (!o || !(o->flags & DQP_FLAG_BATCH_TERMINATION) || stepped_params(md, o, P) != DQP_OK || md->nbatch <= 0) return 0;
-    return term_bytes(P.B, P.maxIter, ric_snapshot_doubles(P.mn, P.mm, P.mT));
+    return term_bytes(P.B, P.maxIter, stage_snapshot_doubles(P.mn, P.mm, P.mT));
 }
 
 __attribute__((visibility("default"))) int
@@ -1063,9 +1080,10 @@ dqp_mpc_qp_forward_stepped(const dqp_mpc_dims *md, const dqp_opts *opts, const d
     if (batch) {
         if (!termination || P.maxIter > 64) return DQP_ERR_BAD_ARG;
         P.eps = opts ? opts->eps : 1e-12;
-        term_bind_pass1(P, termination, ric_snapshot_doubles(P.mn, P.mm, P.mT));
+        term_bind_pass1(P, termination, stage_snapshot_doubles(P.mn, P.mm, P.mT));
     }
-    if ((rc = ric_forward_stepped(P, stream)) != DQP_OK) return rc == 1 ? DQP_ERR_TOO_LARGE : rc;
+    rc = ric_supported(P.mn, P.mm) ? ric_forward_stepped(P, stream) : ricw_forward_stepped(P, stream);
+    if (rc != DQP_OK) return rc == 1 ? DQP_ERR_TOO_LARGE : rc;
     if (it_end < P.maxIter || !batch || (P.flags & DQP_FLAG_HISTORY_ONLY)) return DQP_OK;
     if ((rc = term_decide(P, termination, stream)) != DQP_OK) return rc;
     term_bind_pass2(P, termination);
@@ -1093,7 +1111,7 @@ dqp_mpc_qp_backward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *
     if (kind == MPC_R16N) return r16n_backward(P, stream);
     if (!C || !F) return DQP_ERR_BAD_ARG;
     P.mC = C; P.mF = F;
-    return ric_backward(P, stream);
+    return kind == MPC_RICW ? ricw_backward(P, stream) : ric_backward(P, stream);
 }
 
 __attribute__((visibility("default"))) int

@@ -27,6 +27,8 @@
 // a caller workspace (dqp_mpc_qp_workspace_bytes) -- the kernel is HBM-stream bound by C, F and the
 // factors (~60 k doubles per QP and iteration at config 4), so every knot's matrices are prefetched one
 // knot ahead by LDS-DMA (Stage<C>); short horizons run entirely out of LDS (Cfg<n, m, true>).
+// Knots of 17 to 32 variables take a 32-lane half-wavefront each, two QPs per wavefront (Cfg::G, Cfg::Q; the
+// instantiations are in dqp_ric_wide.hip, which includes this file's templates).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -41,12 +43,55 @@ namespace ric {
 
 using namespace dqp::r16;
 
+#ifndef DQP_RIC_WPE
+#define DQP_RIC_WPE 2
+#endif
+
+// Cross-lane primitives over the G lanes of one problem.  G = 16: the DPP row ones.  G = 32 (two rows):
+// the row's own DPP result, then v_permlane16_swap of two copies of it, which swaps the odd rows of the
+// first with the even rows of the second -- the first then holds row 0's value of each half-wavefront,
+// the second row 1's, in all 32 lanes of the half (the compiler places the VALU-write wait states).
+__device__ __forceinline__ void half_rows(double x, double &row0, double &row1)
+{
+    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(x), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(x), false, false);
+    row0 = __hiloint2double(hi[0], lo[0]);
+    row1 = __hiloint2double(hi[1], lo[1]);
+}
+// value of lane k of the problem's lanes, in all of them (k a compile-time constant after unrolling)
+template <int G> __device__ __forceinline__ double bc(double v, int k)
+{
+    if constexpr (G == 16) return rb(v, k);
+    double a, b;
+    half_rows(rb(v, k & 15), a, b);
+    return k < 16 ? a : b;
+}
+template <int G> __device__ __forceinline__ double gsum(double v)
+{
+    if constexpr (G == 16) return row_sum(v);
+    double a, b;
+    half_rows(row_sum(v), a, b);
+    return a + b;
+}
+template <int G> __device__ __forceinline__ double gmin(double v)
+{
+    if constexpr (G == 16) return row_min(v);
+    double a, b;
+    half_rows(row_min(v), a, b);
+    return fmin(a, b);
+}
+
 // WSL: the per-QP workspace (iterates, directions, factors) lives in LDS instead of the caller's buffer --
 // the forward kernel of short horizons, where it fits beside the stage and a knot step is latency, not bandwidth
 template <int NX_, int NU_, bool WSL_ = false> struct Cfg {
     static constexpr int NX = NX_, NU = NU_, NT = NX_ + NU_;
     static constexpr bool WSL = WSL_;
-    static_assert(NT <= 16, "a knot must fit a 16-lane DPP row");
+    // lanes per problem: one 16-lane DPP row (four problems per wavefront), or above 16 a 32-lane
+    // half-wavefront of two rows (two problems per wavefront: the wide pairs, dqp_ric_wide.hip)
+    static constexpr int G = NT <= 16 ? 16 : 32, Q = 64 / G;
+    static constexpr int WPE = G == 16 ? DQP_RIC_WPE : 1;      // the wide knot needs the whole register file
+    static_assert(NT <= 32, "a knot must fit a 32-lane half-wavefront");
+    static_assert(G == 16 || !WSL, "no LDS-resident workspace for the wide knot");
 };
 
 // per-QP workspace (doubles); everything knot-major
@@ -92,11 +137,11 @@ template <class C> struct Ctx {
     double *w0;                     // workspace of place 0 (places are L.total doubles apart)
     double *img;                    // the wavefront's LDS stage (Stage<C>); WSL: every knot's C_t, then every F_t
     int rf;                         // WSL: where the F_t images start in img
-    const double *lc, *lf;          // WSL: c and f of the four problems, [(t * 4 + place) * NT or NX + r]
-    __device__ const double *imgC(int t) const { return C::WSL ? img + t * (4 * C::NT * C::NT) : img; }
+    const double *lc, *lf;          // WSL: c and f of the Q problems, [(t * Q + place) * NT or NX + r]
+    __device__ const double *imgC(int t) const { return C::WSL ? img + t * (C::Q * C::NT * C::NT) : img; }
     __device__ const double *imgF(int t) const;
-    __device__ double cvec(int t) const { return C::WSL ? lc[(t * 4 + g) * C::NT + r] : P.mc[((long long)t * P.B + qp) * C::NT + r]; }
-    __device__ double fvec(int t) const { return C::WSL ? lf[(t * 4 + g) * C::NX + r] : P.mf[((long long)t * P.B + qp) * C::NX + r]; }
+    __device__ double cvec(int t) const { return C::WSL ? lc[(t * C::Q + g) * C::NT + r] : P.mc[((long long)t * P.B + qp) * C::NT + r]; }
+    __device__ double fvec(int t) const { return C::WSL ? lf[(t * C::Q + g) * C::NX + r] : P.mf[((long long)t * P.B + qp) * C::NX + r]; }
     // knot t of the wavefront's four problems: contiguous in the (T, B, ., .) inputs
     __device__ const double *Cblk(int t) const { return P.mC + ((long long)t * P.B + qp0) * (C::NT * C::NT); }
     __device__ const double *Fblk(int t) const { return P.mF + ((long long)t * P.B + qp0) * (C::NX * C::NT); }
@@ -140,13 +185,14 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// one kind of matrix in the stage: rows of RL doubles
-template <int RL> struct Img {
+// one kind of matrix in the stage: rows of RL doubles, Q problems
+template <int RL, int Q = 4> struct Img {
     static constexpr int PIECE = (RL % 2 == 0) ? 16 : 4;            // bytes per lane of one DMA instruction
     static constexpr int PPR = RL * 8 / PIECE;                       // pieces per matrix row
     // rows of 2^k 16-byte pieces start on few distinct bank groups: piece j of row `row` sits at j ^ swz(row)
-    static constexpr int SWZ_DIV = (PIECE == 16 && PPR > 1 && PPR <= 8 && (PPR & (PPR - 1)) == 0) ? 16 / PPR : 0;
-    static constexpr int doubles(int rows) { return (4 * rows * PPR + 63) / 64 * 64 * PIECE / 8; }   // image of four problems
+    // (256-byte rows, NT = 32: sixteen pieces, swz = row & 15 -- sixteen consecutive rows cover all 64 banks)
+    static constexpr int SWZ_DIV = (PIECE == 16 && PPR > 1 && PPR <= 16 && (PPR & (PPR - 1)) == 0) ? 16 / PPR : 0;
+    static constexpr int doubles(int rows) { return (Q * rows * PPR + 63) / 64 * 64 * PIECE / 8; }   // image of Q problems
     __device__ __forceinline__ static int swz(int row) { return SWZ_DIV ? (row / (SWZ_DIV ? SWZ_DIV : 1)) & (PPR - 1) : 0; }
     // columns [C0, C1) of row `row` of place g.  With the swizzle, piece j of the row is at index
     // (base | s << 1) ^ (j << 1) (base is a multiple of the row length 2 PPR, a power of two there): one
@@ -185,11 +231,18 @@ template <int RL> struct Img {
             else out[i] = img[root + i * RL];
         }
     }
+    // the LDS address of a pointer into the stage.  Q = 2 takes it through an integer: there this compiler
+    // folds the plain cast's null check into an illegal `v_cmp_ne_u32 0, src_shared_base` and stops
+    __device__ __forceinline__ static lvoid_t *lds_ptr(double *p)
+    {
+        if constexpr (Q == 4) return (lvoid_t *)p;
+        else return (lvoid_t *)(uintptr_t)(uint32_t)(uintptr_t)p;
+    }
     // issue the DMA of one knot's ROWS x RL matrices: place q's matrix is at base + min(q, qmax) * qstride_bytes
     template <int ROWS>
     __device__ __forceinline__ static void fetch(double *img, const double *base, int qstride_bytes, int qmax, int lane)
     {
-        constexpr int PIECES = 4 * ROWS * PPR, KN = (PIECES + 63) / 64;
+        constexpr int PIECES = Q * ROWS * PPR, KN = (PIECES + 63) / 64;
 #pragma unroll
         for (int k = 0; k < KN; ++k) {
             int p = k * 64 + lane;
@@ -197,7 +250,7 @@ template <int RL> struct Img {
             const int rowg = p / PPR, j = p % PPR, q = rowg / ROWS, row = rowg % ROWS;
             const int off = (q < qmax ? q : qmax) * qstride_bytes + (row * PPR + (j ^ swz(row))) * PIECE;
             gvoid_t *src = (gvoid_t *)(reinterpret_cast<const char *>(base) + off);
-            lvoid_t *dst = (lvoid_t *)(img + k * (64 * PIECE / 8));
+            lvoid_t *dst = lds_ptr(img + k * (64 * PIECE / 8));
             if constexpr (PIECE == 16) __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
             else __builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);
         }
@@ -208,7 +261,7 @@ template <int RL> struct Img {
     __device__ __forceinline__ static void fetch_all(double *img, const double *base, long long tstride_bytes, int qstride_bytes,
                                                      int qmax, int lane, int count)
     {
-        constexpr int PIECES = 4 * ROWS * PPR;
+        constexpr int PIECES = Q * ROWS * PPR;
         const int total = count * PIECES;
         for (int k = 0; k * 64 < total; ++k) {
             int p = k * 64 + lane;
@@ -217,42 +270,42 @@ template <int RL> struct Img {
             const int rowg = pp / PPR, j = pp % PPR, q = rowg / ROWS, row = rowg % ROWS;
             const long long off = t * tstride_bytes + (q < qmax ? q : qmax) * qstride_bytes + (row * PPR + (j ^ swz(row))) * PIECE;
             gvoid_t *src = (gvoid_t *)(reinterpret_cast<const char *>(base) + off);
-            lvoid_t *dst = (lvoid_t *)(img + k * (64 * PIECE / 8));
+            lvoid_t *dst = lds_ptr(img + k * (64 * PIECE / 8));
             if constexpr (PIECE == 16) __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
             else __builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);
         }
     }
-    static constexpr __host__ __device__ int resident_doubles(int rows, int count) { return (count * 4 * rows * PPR + 63) / 64 * 64 * PIECE / 8; }
+    static constexpr __host__ __device__ int resident_doubles(int rows, int count) { return (count * Q * rows * PPR + 63) / 64 * 64 * PIECE / 8; }
 };
 
 // the wavefront's image: [C_t | F_t] while factorising, [P_t | L_t | F_t] in the vector sweeps
 template <class C> struct Stage {
     static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
-    using MC = Img<NT>;             // C_t: NT rows of NT
-    using MF = Img<NT>;             // F_t: NX rows of NT
-    using MP = Img<NX>;             // cost-to-go P_t: NX rows of NX
-    using ML = Img<NU>;             // [Lxu ; Luu] with 1 / L_jj on the diagonal: NT rows of NU
+    using MC = Img<NT, C::Q>;       // C_t: NT rows of NT
+    using MF = Img<NT, C::Q>;       // F_t: NX rows of NT
+    using MP = Img<NX, C::Q>;       // cost-to-go P_t: NX rows of NX
+    using ML = Img<NU, C::Q>;       // [Lxu ; Luu] with 1 / L_jj on the diagonal: NT rows of NU
     static constexpr int OL = MP::doubles(NX);
     static constexpr int OF = MC::doubles(NT) > OL + ML::doubles(NT) ? MC::doubles(NT) : OL + ML::doubles(NT);
     static constexpr int TOTAL = OF + MF::doubles(NX);
     // WSL (everything of a short-horizon problem in LDS): [C_0 .. C_{T-1} | F_0 .. F_{T-2} | c | f | four workspaces]
     static __host__ __device__ int res_f(int T) { return MC::resident_doubles(NT, T); }
     static __host__ __device__ int res_c(int T) { return res_f(T) + MF::resident_doubles(NX, T - 1 > 0 ? T - 1 : 1); }
-    static __host__ __device__ int res_fv(int T) { return res_c(T) + T * 4 * NT; }
-    static __host__ __device__ int res_ws(int T) { return (res_fv(T) + T * 4 * NX + 1) & ~1; }
+    static __host__ __device__ int res_fv(int T) { return res_c(T) + T * C::Q * NT; }
+    static __host__ __device__ int res_ws(int T) { return (res_fv(T) + T * C::Q * NX + 1) & ~1; }
 };
 
 template <class C> __device__ __forceinline__ const double *Ctx<C>::imgF(int t) const
 {
-    return C::WSL ? img + rf + t * (4 * C::NX * C::NT) : img + Stage<C>::OF;
+    return C::WSL ? img + rf + t * (C::Q * C::NX * C::NT) : img + Stage<C>::OF;
 }
 
 // y[r] = sum_c row[c] * v[c]  (row = this lane's matrix row, v distributed)
-template <int N> __device__ __forceinline__ double mv_row(const double (&row)[N], double v)
+template <int N, int G> __device__ __forceinline__ double mv_row(const double (&row)[N], double v)
 {
     double acc = 0.0;
 #pragma unroll
-    for (int c = 0; c < N; ++c) acc = fma(row[c], rb(v, c), acc);
+    for (int c = 0; c < N; ++c) acc = fma(row[c], bc<G>(v, c), acc);
     return acc;
 }
 
@@ -268,14 +321,14 @@ __device__ __forceinline__ void add_FtPF(double (&H)[C::NT], const double (&Pn)[
     for (int j = 0; j < NT; ++j) {                  // PF = P_{t+1} F_t, row-distributed over the state lanes
         double acc = 0.0;
 #pragma unroll
-        for (int c = 0; c < NX; ++c) acc = fma(Pn[c], rb(frow[j], c), acc);
+        for (int c = 0; c < NX; ++c) acc = fma(Pn[c], bc<C::G>(frow[j], c), acc);
         PF[j] = acc;
     }
 #pragma unroll
     for (int b = 0; b < NT; ++b) {
         double acc = H[b];
 #pragma unroll
-        for (int i = 0; i < NX; ++i) acc = fma(fcol[i], rb(PF[b], i), acc);
+        for (int i = 0; i < NX; ++i) acc = fma(fcol[i], bc<C::G>(PF[b], i), acc);
         H[b] = acc;
     }
 }
@@ -310,8 +363,8 @@ template <class C, bool WITHP> __device__ __forceinline__ void fetch_facF(const 
 {
     using S = Stage<C>;
     if constexpr (C::WSL) return;
-    if (WITHP) S::MP::template fetch<C::NX>(K.img, K.Pblk(t), K.L.total * 8, 3, K.lane);
-    S::ML::template fetch<C::NT>(K.img + S::OL, K.Lblk(t), K.L.total * 8, 3, K.lane);
+    if (WITHP) S::MP::template fetch<C::NX>(K.img, K.Pblk(t), K.L.total * 8, C::Q - 1, K.lane);
+    S::ML::template fetch<C::NT>(K.img + S::OL, K.Lblk(t), K.L.total * 8, C::Q - 1, K.lane);
     if (t < K.T - 1) S::MF::template fetch<C::NX>(K.img + S::OF, K.Fblk(t), C::NX * C::NT * 8, K.qmax, K.lane);
 }
 // this lane's row of [Lxu ; Luu] of knot t and, on a control lane, 1 / L_jj (kept on the diagonal)
@@ -400,14 +453,14 @@ __device__ __forceinline__ bool factor(const Ctx<C> &K0, bool unit, bool clampd)
         double rdj_keep = 0.0;
 #pragma unroll
         for (int j = NX; j < NT; ++j) {
-            const double pj = rb(H[j], j);
+            const double pj = bc<C::G>(H[j], j);
             if (!(pj > 0.0)) ok = false;
             const double rdj = frsqrt(pj > 0.0 ? pj : 1.0);
             const double lij = H[j] * rdj;                  // column j of L on every lane (lane j: sqrt(pj))
 #pragma unroll
             for (int c = 0; c < NT; ++c) {
                 if (c >= NX && c <= j) continue;            // L columns already final
-                H[c] = fma(-lij, rb(lij, c), H[c]);
+                H[c] = fma(-lij, bc<C::G>(lij, c), H[c]);
             }
             H[j] = lij;
             if (r == j) rdj_keep = rdj;
@@ -433,7 +486,7 @@ __device__ __forceinline__ void model_residuals_of(const Ctx<C> &K)
         constexpr int NX = C::NX, NT = C::NT;
         double *w = K.w;
         const Lay &L = K.L;
-        for (int base = 0; base < K.T - 1; base += 16) {
+        for (int base = 0; base < K.T - 1; base += C::G) {
             const int t = base + K.r;
             if (t < K.T - 1) {
                 double z[NT], xn[NX];
@@ -525,7 +578,7 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
         const double tau = cur[V_TAU];
 #pragma unroll
         for (int c = 0; c < NT; ++c) H[c] = r < NT ? H[c] : 0.0;
-        double rx = mv_row<NT>(H, tau) + cur[V_MC];
+        double rx = mv_row<NT, C::G>(H, tau) + cur[V_MC];
         double q = 0.0, e = 0.0;
         if (K.ul) {
             const int iu = t * NU + K.a;
@@ -545,11 +598,11 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
         if (t < T - 1) {
             double acc = 0.0;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], rb(y_t, i), acc);
+            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], bc<C::G>(y_t, i), acc);
             rx += acc;
             // ry_t: the linearised dynamics, or the registered model's own residual (computed by model_residuals)
             double fx = 0.0;
-            if constexpr (!DYN) fx = mv_row<NT>(frow, tau) + cur[V_MF];       // (row broadcasts: every lane takes part)
+            if constexpr (!DYN) fx = mv_row<NT, C::G>(frow, tau) + cur[V_MF];       // (row broadcasts: every lane takes part)
             if (K.xl) {
                 if constexpr (DYN) e = cur[V_MF];
                 else {
@@ -576,28 +629,28 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
         if (t < T - 1) {
             double v = pn;
 #pragma unroll
-            for (int c = 0; c < NX; ++c) v = fma(Pn[c], rb(e, c), v);
+            for (int c = 0; c < NX; ++c) v = fma(Pn[c], bc<C::G>(e, c), v);
             double acc = 0.0;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], rb(v, i), acc);
+            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], bc<C::G>(v, i), acc);
             h += acc;
         }
         // ---- partial Cholesky on the control pivots, the same elimination on h
         double rdj_keep = 0.0;
 #pragma unroll
         for (int j = NX; j < NT; ++j) {
-            const double pj = rb(H[j], j);
+            const double pj = bc<C::G>(H[j], j);
             if (!(pj > 0.0)) ok = false;
             const double rdj = frsqrt(pj > 0.0 ? pj : 1.0);
             const double lij = H[j] * rdj;
 #pragma unroll
             for (int c = 0; c < NT; ++c) {
                 if (c >= NX && c <= j) continue;
-                H[c] = fma(-lij, rb(lij, c), H[c]);
+                H[c] = fma(-lij, bc<C::G>(lij, c), H[c]);
             }
             H[j] = lij;
             if (r == j) rdj_keep = rdj;
-            const double hj = rb(h, j) * rdj;
+            const double hj = bc<C::G>(h, j) * rdj;
             h = (r == j) ? hj : ((r < NX || (r > j && r < NT)) ? fma(-lij, hj, h) : h);
         }
         store_fac<C>(K, w, t, H, rdj_keep);
@@ -688,16 +741,16 @@ __device__ __forceinline__ void sweep_back(const Ctx<C> &K0, double musig)
             if (USE_E) {
                 const double e = cur[R_H];
 #pragma unroll
-                for (int c = 0; c < NX; ++c) v = fma(Pn[c], rb(e, c), v);
+                for (int c = 0; c < NX; ++c) v = fma(Pn[c], bc<C::G>(e, c), v);
             }
             double acc = 0.0;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], rb(v, i), acc);
+            for (int i = 0; i < NX; ++i) acc = fma(fcol[i], bc<C::G>(v, i), acc);
             h += acc;
         }
 #pragma unroll
         for (int j = NX; j < NT; ++j) {
-            const double hj = rb(h, j) * rb(rd, j);
+            const double hj = bc<C::G>(h, j) * bc<C::G>(rd, j);
             const double lij = (r < NT && (r < NX || r > j)) ? lcol[j - NX] : 0.0;
             h = (r == j) ? hj : fma(-lij, hj, h);
         }
@@ -774,7 +827,7 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
             const double dxs = (MODE == CORRECTOR) ? dx + (K.xl ? cur[V_DXO] : 0.0) : dx;        // affine + corrector
             double v = cur[V_PV];
 #pragma unroll
-            for (int c = 0; c < NX; ++c) v = fma(K.xl ? prow[c] : 0.0, rb(dxs, c), v);
+            for (int c = 0; c < NX; ++c) v = fma(K.xl ? prow[c] : 0.0, bc<C::G>(dxs, c), v);
             if (t == 0) v = -v;
             if (K.xl) w[L.DY + (t >= 1 ? t - 1 : T - 1) * NX + r] = v;
         }
@@ -783,13 +836,13 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
         double zz = K.ul ? cur[V_YB] : 0.0;
 #pragma unroll
         for (int b = 0; b < NU; ++b) {
-            const double wb = row_sum(K.xl ? lrow[b] * dx : 0.0);        // (Lxu' dx)[b]
+            const double wb = gsum<C::G>(K.xl ? lrow[b] * dx : 0.0);        // (Lxu' dx)[b]
             if (r == NX + b) zz += wb;
         }
         double yv = 0.0;                                                   // Luu' yv = zz
 #pragma unroll
         for (int j = NT - 1; j >= NX; --j) {
-            const double s = row_sum((r > j && r < NT) ? lrow[j - NX] * yv : 0.0);
+            const double s = gsum<C::G>((r > j && r < NT) ? lrow[j - NX] * yv : 0.0);
             if (r == j) yv = (zz - s) * rd;
         }
         const double dtau = K.xl ? dx : (K.ul ? -yv : 0.0);
@@ -829,7 +882,7 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
         if (t < T - 1) {
 #pragma unroll
             for (int c = 0; c < NT; ++c) frow[c] = K.xl ? frow[c] : 0.0;
-            const double dxn = mv_row<NT>(frow, dtau) + (USE_E ? cur[V_E] : 0.0);
+            const double dxn = mv_row<NT, C::G>(frow, dtau) + (USE_E ? cur[V_E] : 0.0);
             dx = K.xl ? dxn : 0.0;
         }
 #pragma unroll
@@ -838,54 +891,56 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
     return ratio;
 }
 
-// element-wise helpers over per-QP arrays, lanes strided.  A plain `for (i = r; i < n; i += 16) dst[i] = src[i]`
+// element-wise helpers over per-QP arrays, lanes strided.  A plain `for (i = r; i < n; i += G) dst[i] = src[i]`
 // waits out one memory latency per element (nothing tells the compiler that dst and src are different
 // regions of the workspace); these keep EW_DEPTH independent loads per lane in flight -- the passes
 // between the sweeps were 15-20 % of an iteration at four.
 constexpr int EW_DEPTH = 16;
+template <int G>
 __device__ __forceinline__ void ew_copy(double *__restrict__ dst, double *__restrict__ dst2, const double *__restrict__ src,
                                         int n, int r)
 {
     int i = r;
-    for (; i + 16 * (EW_DEPTH - 1) < n; i += 16 * EW_DEPTH) {
+    for (; i + G * (EW_DEPTH - 1) < n; i += G * EW_DEPTH) {
         double v[EW_DEPTH];
 #pragma unroll
-        for (int k = 0; k < EW_DEPTH; ++k) v[k] = src[i + 16 * k];
+        for (int k = 0; k < EW_DEPTH; ++k) v[k] = src[i + G * k];
 #pragma unroll
-        for (int k = 0; k < EW_DEPTH; ++k) dst[i + 16 * k] = v[k];
+        for (int k = 0; k < EW_DEPTH; ++k) dst[i + G * k] = v[k];
         if (dst2) {
 #pragma unroll
-            for (int k = 0; k < EW_DEPTH; ++k) dst2[i + 16 * k] = v[k];
+            for (int k = 0; k < EW_DEPTH; ++k) dst2[i + G * k] = v[k];
         }
     }
     double v[EW_DEPTH];
 #pragma unroll
-    for (int k = 0; k < EW_DEPTH; ++k) v[k] = i + 16 * k < n ? src[i + 16 * k] : 0.0;
+    for (int k = 0; k < EW_DEPTH; ++k) v[k] = i + G * k < n ? src[i + G * k] : 0.0;
 #pragma unroll
     for (int k = 0; k < EW_DEPTH; ++k) {
-        if (i + 16 * k < n) {
-            dst[i + 16 * k] = v[k];
-            if (dst2) dst2[i + 16 * k] = v[k];
+        if (i + G * k < n) {
+            dst[i + G * k] = v[k];
+            if (dst2) dst2[i + G * k] = v[k];
         }
     }
 }
+template <int G>
 __device__ __forceinline__ void ew_axpy(double *__restrict__ y, const double *__restrict__ x, double alpha, int n, int r)
 {
     constexpr int D = EW_DEPTH / 2;
     int i = r;
-    for (; i + 16 * (D - 1) < n; i += 16 * D) {
+    for (; i + G * (D - 1) < n; i += G * D) {
         double xv[D], yv[D];
 #pragma unroll
-        for (int k = 0; k < D; ++k) { xv[k] = x[i + 16 * k]; yv[k] = y[i + 16 * k]; }
+        for (int k = 0; k < D; ++k) { xv[k] = x[i + G * k]; yv[k] = y[i + G * k]; }
 #pragma unroll
-        for (int k = 0; k < D; ++k) y[i + 16 * k] = fma(alpha, xv[k], yv[k]);
+        for (int k = 0; k < D; ++k) y[i + G * k] = fma(alpha, xv[k], yv[k]);
     }
     double xv[D], yv[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) { const bool in = i + 16 * k < n; xv[k] = in ? x[i + 16 * k] : 0.0; yv[k] = in ? y[i + 16 * k] : 0.0; }
+    for (int k = 0; k < D; ++k) { const bool in = i + G * k < n; xv[k] = in ? x[i + G * k] : 0.0; yv[k] = in ? y[i + G * k] : 0.0; }
 #pragma unroll
     for (int k = 0; k < D; ++k)
-        if (i + 16 * k < n) y[i + 16 * k] = fma(alpha, xv[k], yv[k]);
+        if (i + G * k < n) y[i + G * k] = fma(alpha, xv[k], yv[k]);
 }
 
 // the iterate (X, Y, SU, SL, ZU, ZL: contiguous at the head of the layout) -> the best-iterate arrays, or,
@@ -900,26 +955,23 @@ __device__ __forceinline__ void copy_best(const Ctx<C> &K, double *snap)
     const int T = K.T, r = K.r;
     const int len = T * (NT + NX + 4 * NU);
     if (snap) {
-        if (K.live) ew_copy(snap, nullptr, w + L.X, len, r);
+        if (K.live) ew_copy<C::G>(snap, nullptr, w + L.X, len, r);
     } else {
-        ew_copy(w + L.BX, nullptr, w + L.X, len, r);      // BX, BY, BSU, BSL, BZU, BZL mirror X .. ZL
+        ew_copy<C::G>(w + L.BX, nullptr, w + L.X, len, r);      // BX, BY, BSU, BSL, BZU, BZL mirror X .. ZL
     }
 }
 
-#ifndef DQP_RIC_WPE
-#define DQP_RIC_WPE 2
-#endif
 // DYN: 0 the equality residual is A z - b; 1 a registered model's own step (model_residuals); 2 supplied by the
 // caller, one iteration range [P.itBegin, P.itEnd) per launch, the scalar state of the loop parked behind the workspaces
 // (dqp_mpc_qp_forward_stepped)
 enum { RES_LINEAR = 0, RES_MODEL = 1, RES_CALLER = 2 };
 constexpr int STEP_STATE = 8;      // doubles per problem slot
 template <class C, int DYN>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE, DQP_RIC_WPE))) void forward_kernel(KParams P, int T)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C::WPE, C::WPE))) void forward_kernel(KParams P, int T)
 {
-    constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
-    const int lane = threadIdx.x, r = lane & 15;
-    long long qp = (long long)blockIdx.x * 4 + (lane >> 4);
+    constexpr int NX = C::NX, NU = C::NU, NT = C::NT, G = C::G, Q = C::Q;
+    const int lane = threadIdx.x, r = lane & (G - 1);
+    long long qp = (long long)blockIdx.x * Q + lane / G;
     bool live = qp < P.B;
     if (!live) qp = P.B - 1;
     int maxIter = P.maxIter;
@@ -932,27 +984,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
     term_zero_acc(P);
     const Lay L = layout(NX, NU, T);
     // a duplicated (padding) row works on its own copy of the last problem's scratch: rows must not race
-    const long long slot = (long long)blockIdx.x * 4 + (lane >> 4);
+    const long long slot = (long long)blockIdx.x * Q + lane / G;
     __shared__ __attribute__((aligned(16))) double lds_img[C::WSL ? 2 : Stage<C>::TOTAL];
     using S = Stage<C>;
     double *img = C::WSL ? lds_dyn : lds_img;
-    const long long qp0 = (long long)blockIdx.x * 4;
+    const long long qp0 = (long long)blockIdx.x * Q;
     double *ws0 = C::WSL ? lds_dyn + S::res_ws(T) : P.workspace + qp0 * (long long)L.total;
-    Ctx<C> K = {P, ws0 + (lane >> 4) * (long long)L.total, L, qp, r, T, r < NX, r >= NX && r < NT, live,
+    Ctx<C> K = {P, ws0 + lane / G * (long long)L.total, L, qp, r, T, r < NX, r >= NX && r < NT, live,
                 (r >= NX && r < NT) ? r - NX : 0, 0.0, 0.0,
-                lane, lane >> 4, (int)min(3LL, (long long)P.B - 1 - qp0), qp0, ws0, img,
+                lane, lane / G, (int)min((long long)Q - 1, (long long)P.B - 1 - qp0), qp0, ws0, img,
                 S::res_f(T), lds_dyn + S::res_c(T), lds_dyn + S::res_fv(T)};
     K.uu = P.muu[K.a]; K.ulo = P.mul[K.a];
     if constexpr (C::WSL) {     // the whole problem into LDS, once
         S::MC::template fetch_all<NT>(img, K.Cblk(0), (long long)P.B * NT * NT * 8, NT * NT * 8, K.qmax, lane, T);
         if (T > 1) S::MF::template fetch_all<NX>(img + K.rf, K.Fblk(0), (long long)P.B * NX * NT * 8, NX * NT * 8, K.qmax, lane, T - 1);
         double *lc = lds_dyn + S::res_c(T), *lf = lds_dyn + S::res_fv(T);
-        for (int i = lane; i < T * 4 * NT; i += 64) {
-            const int t = i / (4 * NT), gq = (i / NT) % 4, rr = i % NT;
+        for (int i = lane; i < T * Q * NT; i += 64) {
+            const int t = i / (Q * NT), gq = (i / NT) % Q, rr = i % NT;
             lc[i] = P.mc[((long long)t * P.B + qp0 + min(gq, K.qmax)) * NT + rr];
         }
-        for (int i = lane; i < (T - 1) * 4 * NX; i += 64) {
-            const int t = i / (4 * NX), gq = (i / NX) % 4, rr = i % NX;
+        for (int i = lane; i < (T - 1) * Q * NX; i += 64) {
+            const int t = i / (Q * NX), gq = (i / NX) % Q, rr = i % NX;
             lf[i] = P.mf[((long long)t * P.B + qp0 + min(gq, K.qmax)) * NX + rr];
         }
         wait_vm();
@@ -963,7 +1015,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
 
     constexpr bool STEPPED = DYN == RES_CALLER;
     const int it0 = STEPPED ? P.itBegin : 0, it1 = STEPPED ? min(P.itEnd, maxIter) : maxIter;
-    double *stp = STEPPED ? P.workspace + (long long)gridDim.x * 4 * L.total + slot * STEP_STATE : nullptr;
+    double *stp = STEPPED ? P.workspace + (long long)gridDim.x * Q * L.total + slot * STEP_STATE : nullptr;
 
     // ---- initial point (batch.py:60-86)
     if (!STEPPED || it0 == 0) {
@@ -971,15 +1023,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
     sweep_back<C, INIT>(K, 0.0);
     sweep_fwd<C, INIT>(K, 0.0);
     {
-        ew_copy(w + L.X, nullptr, w + L.DX, T * NT, r);
-        ew_copy(w + L.Y, nullptr, w + L.DY, T * NX, r);
+        ew_copy<C::G>(w + L.X, nullptr, w + L.DX, T * NT, r);
+        ew_copy<C::G>(w + L.Y, nullptr, w + L.DY, T * NX, r);
         double ms = INFINITY, mz = INFINITY;
-        for (int i = r; i < T * NU; i += 16) {
+        for (int i = r; i < T * NU; i += G) {
             ms = fmin(ms, fmin(w[L.SU + i], w[L.SL + i]));
             mz = fmin(mz, fmin(w[L.ZU + i], w[L.ZL + i]));
         }
-        ms = row_min(ms); mz = row_min(mz);
-        for (int i = r; i < T * NU; i += 16) {
+        ms = gmin<C::G>(ms); mz = gmin<C::G>(mz);
+        for (int i = r; i < T * NU; i += G) {
             if (ms < 0.0) { w[L.SU + i] -= ms - 1.0; w[L.SL + i] -= ms - 1.0; }
             if (mz < 0.0) { w[L.ZU + i] -= mz - 1.0; w[L.ZL + i] -= mz - 1.0; }
         }
@@ -1000,10 +1052,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
         if constexpr (DYN == RES_MODEL) model_residuals<C>(K);
         if constexpr (STEPPED) {    // the caller's dyn_res(x) of this iterate, closure ordering = this layout's
             const double *ery = P.extRy + qp * (long long)(T * NX);
-            for (int i = r; i < (T - 1) * NX; i += 16) w[L.RY + i] = ery[i];
+            for (int i = r; i < (T - 1) * NX; i += G) w[L.RY + i] = ery[i];
         }
         const bool pd = factor_fused<C, DYN != RES_LINEAR>(K, nx2, nz2, ny2, sz);      // residuals + factorisation + affine rhs
-        nx2 = row_sum(nx2); nz2 = row_sum(nz2); ny2 = row_sum(ny2); sz = row_sum(sz);
+        nx2 = gsum<C::G>(nx2); nz2 = gsum<C::G>(nz2); ny2 = gsum<C::G>(ny2); sz = gsum<C::G>(sz);
         const double mu = fabs(sz / nineq);
         const double resid = sqrt(nz2) + sqrt(ny2) + sqrt(nx2) + nineq * mu;
         if (!done) {
@@ -1024,25 +1076,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
 
         if (!pd && status == DQP_STATUS_OK) status = DQP_STATUS_Q_NOT_PD;
         // affine direction and its step (batch.py:147-163)
-        double ra = row_min(sweep_fwd<C, AFFINE>(K, 0.0));
+        double ra = gmin<C::G>(sweep_fwd<C, AFFINE>(K, 0.0));
         const bool zero_step = ra == -INFINITY;     // strict get_step only
         const double alpha_a = fmin(ra, 1.0);
         double t3 = 0.0;
 #pragma unroll 4
-        for (int i = r; i < T * NU; i += 16) {
+        for (int i = r; i < T * NU; i += G) {
             t3 = fma(w[L.SU + i] + alpha_a * w[L.DSU + i], w[L.ZU + i] + alpha_a * w[L.DZU + i], t3);
             t3 = fma(w[L.SL + i] + alpha_a * w[L.DSL + i], w[L.ZL + i] + alpha_a * w[L.DZL + i], t3);
         }
-        t3 = row_sum(t3);
+        t3 = gsum<C::G>(t3);
         double sig = t3 / sz;
         sig = sig * sig * sig;
         // corrector (batch.py:165-181), step (batch.py:183-204)
         sweep_back<C, CORRECTOR>(K, mu * sig);
-        const double rc = row_min(sweep_fwd<C, CORRECTOR>(K, mu * sig));
+        const double rc = gmin<C::G>(sweep_fwd<C, CORRECTOR>(K, mu * sig));
         const double alpha = fmin(0.999 * rc, 1.0);
         if (zero_step || rc == -INFINITY) done = true;      // the reference's iterate is NaN from here: keep the best
         if (!done)          // X .. ZL and DX .. DZL are laid out alike: one axpy over the whole iterate
-            ew_axpy(w + L.X, w + L.DX, alpha, T * (NT + NX + 4 * NU), r);
+            ew_axpy<C::G>(w + L.X, w + L.DX, alpha, T * (NT + NX + 4 * NU), r);
     }
     if (STEPPED) {
         if (r == 0) {
@@ -1052,7 +1104,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
         }
         if (it1 < maxIter) {        // more iterations to come: hand the current iterate to the caller
             if (live)
-                for (int i = r; i < T * NT; i += 16) P.zhat[qp * (long long)(T * NT) + i] = w[L.X + i];
+                for (int i = r; i < T * NT; i += G) P.zhat[qp * (long long)(T * NT) + i] = w[L.X + i];
             return;
         }
     }
@@ -1065,9 +1117,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
         const int nz = T * NT, neq = T * NX, hm = T * NU;
         const double *bx = (P.snap && have_best) ? P.snap + ((long long)best_it * P.B + qp) * (long long)(nz + neq + 4 * hm) : w + L.BX;
         const double *by = bx + nz, *bs = by + neq, *bz = bs + 2 * hm;         // [X | Y | SU SL | ZU ZL]
-        for (int i = r; i < nz; i += 16) P.zhat[qp * nz + i] = bx[i];
-        for (int i = r; i < neq; i += 16) P.nu[qp * neq + i] = by[i];
-        for (int i = r; i < hm; i += 16) {
+        for (int i = r; i < nz; i += G) P.zhat[qp * nz + i] = bx[i];
+        for (int i = r; i < neq; i += G) P.nu[qp * neq + i] = by[i];
+        for (int i = r; i < hm; i += G) {
             P.lam[qp * 2 * hm + i] = bz[i];       P.lam[qp * 2 * hm + hm + i] = bz[hm + i];
             P.slack[qp * 2 * hm + i] = bs[i];     P.slack[qp * 2 * hm + hm + i] = bs[hm + i];
         }
@@ -1084,22 +1136,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DQP_RIC_WPE,
 template <class C>
 __global__ __launch_bounds__(64) void backward_kernel(KParams P, int T)
 {
-    constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
-    const int lane = threadIdx.x, r = lane & 15;
-    long long qp = (long long)blockIdx.x * 4 + (lane >> 4);
+    constexpr int NX = C::NX, NU = C::NU, NT = C::NT, G = C::G, Q = C::Q;
+    const int lane = threadIdx.x, r = lane & (G - 1);
+    long long qp = (long long)blockIdx.x * Q + lane / G;
     const bool live = qp < P.B;
     if (!live) qp = P.B - 1;
     const Lay L = layout(NX, NU, T);
-    const long long slot = (long long)blockIdx.x * 4 + (lane >> 4);
+    const long long slot = (long long)blockIdx.x * Q + lane / G;
     __shared__ __attribute__((aligned(16))) double img[Stage<C>::TOTAL];
-    const long long qp0 = (long long)blockIdx.x * 4;
+    const long long qp0 = (long long)blockIdx.x * Q;
     Ctx<C> K = {P, P.workspace + slot * (long long)L.total, L, qp, r, T, r < NX, r >= NX && r < NT, live,
                 (r >= NX && r < NT) ? r - NX : 0, 0.0, 0.0,
-                lane, lane >> 4, (int)min(3LL, (long long)P.B - 1 - qp0), qp0, P.workspace + qp0 * (long long)L.total, img,
+                lane, lane / G, (int)min((long long)Q - 1, (long long)P.B - 1 - qp0), qp0, P.workspace + qp0 * (long long)L.total, img,
                 0, nullptr, nullptr};
     double *w = K.w;
     const int nz = T * NT, neq = T * NX, hm = T * NU;
-    for (int i = r; i < hm; i += 16) {
+    for (int i = r; i < hm; i += G) {
         w[L.ZU + i] = P.lamin[qp * 2 * hm + i];     w[L.ZL + i] = P.lamin[qp * 2 * hm + hm + i];
         w[L.SU + i] = P.slackin[qp * 2 * hm + i];   w[L.SL + i] = P.slackin[qp * 2 * hm + hm + i];
     }
@@ -1118,7 +1170,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P, int T)
         if (P.mdC) {
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
-                const double v = 0.5 * (rb(dxr, i) * zr + rb(zr, i) * dxr);
+                const double v = 0.5 * (bc<C::G>(dxr, i) * zr + bc<C::G>(zr, i) * dxr);
                 if (r < NT) P.mdC[(((long long)t * Bq + qp) * NT + i) * NT + r] = v;
             }
         }
@@ -1128,7 +1180,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P, int T)
             if (P.mdF) {
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
-                    const double v = rb(dn, i) * zr + rb(nn, i) * dxr;
+                    const double v = bc<C::G>(dn, i) * zr + bc<C::G>(nn, i) * dxr;
                     if (r < NT) P.mdF[(((long long)t * Bq + qp) * NX + i) * NT + r] = v;
                 }
             }
@@ -1139,6 +1191,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P, int T)
     if (r == 0 && P.info) { P.info[2 * qp] = status; P.info[2 * qp + 1] = 0; }
 }
 
+#ifndef DQP_RIC_KERNELS_ONLY     // dqp_ric_wide.hip includes the templates above and instantiates its own pairs
 // Pass 2 of the batch-coupled rule (dqp_term.hip) when pass 1 kept its improving iterates: a flagged
 // problem's outputs are rewritten from the snapshot of its best iteration before the stop -- a copy.
 // One wavefront per problem; sizes at run time.
@@ -1168,16 +1221,18 @@ __global__ __launch_bounds__(64) void finish_kernel(KParams P, int T, int nx, in
         if (P.best_resid) P.best_resid[qp] = best;
     }
 }
+#endif
 
 template <class C, class Kern> int launch(Kern kernel, const KParams &P, int T, void *stream, size_t lds = 0)
 {
-    const int blocks = (P.B + 3) / 4;
+    const int blocks = (P.B + C::Q - 1) / C::Q;
     DQP_LAUNCH(kernel, dim3(blocks), dim3(64), lds, (hipStream_t)stream, P, T);
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
 }  // namespace ric
 
+#ifndef DQP_RIC_KERNELS_ONLY
 // size table: (n_state, n_ctrl) pairs with a stage-wise kernel
 #ifndef DQP_RIC_SIZES
 #define DQP_RIC_SIZES                                                                                   \
@@ -1252,5 +1307,7 @@ int ric_backward(const KParams &P, void *stream)
 #undef X
     return 1;
 }
+
+#endif  // DQP_RIC_KERNELS_ONLY
 
 }  // namespace dqp

@@ -140,7 +140,9 @@ class _AssembleDenseQP(Function):
 class _MPCQP(Function):
     """(C, c, F, f, x0) -> tau (B, T, n+m): assembly + DenseQPFunction (qp_wrapper.py:311-319) as ONE
     solve through dqp_mpc_qp_forward -- the dense (Q,p,G,h,A,b) exists only in registers -- and
-    the backward straight into (dC, dc, dF, df, dx0) (dqp_mpc_qp_backward)."""
+    the backward straight into (dC, dc, dF, df, dx0) (dqp_mpc_qp_backward).  Shapes: small horizons on the
+    null-space kernels, any horizon on the stage-wise ones for a compiled (n_state, n_ctrl) pair with
+    n_state + n_ctrl <= 32 (supported() asks the library)."""
 
     @staticmethod
     def supported(B, n_state, n_ctrl, T, dyn=None):
@@ -211,7 +213,8 @@ class _MPCQPStepped(Function):
     """_MPCQP for a dynamics model the library cannot evaluate (a caller's torch module): the reference calls its
     dyn_res closure once per PDIPM iteration on the current iterate (qp_wrapper.py:309,316 -> batch_LU.py:97).
     Here: one stage-wise PDIPM iteration per C-ABI call (dqp_mpc_qp_forward_stepped), the module evaluated in
-    between on the iterate the call hands back -- one torch evaluation per iteration, everything else on chip."""
+    between on the iterate the call hands back -- one torch evaluation per iteration, everything else on chip.
+    Shapes: the stage-wise pairs, compiled (n_state, n_ctrl) with n_state + n_ctrl <= 32."""
 
     @staticmethod
     def supported(B, n_state, n_ctrl, T):
@@ -447,7 +450,7 @@ class MPC(Module):
                 raise NotImplementedError(
                     "qp_wrapper.MPC with a caller-supplied dynamics module evaluates the module's residual once per "
                     "QP iteration (reference qp_wrapper.py:309,316) around the stage-wise kernels: that needs control "
-                    "bounds, no goal constraint and a compiled (n_state, n_ctrl) pair with n_state + n_ctrl <= 16.  "
+                    "bounds, no goal constraint and a compiled (n_state, n_ctrl) pair with n_state + n_ctrl <= 32.  "
                     "Register the model (dynamics.DeviceDynamics) or pass linearised_residual=True otherwise.")
             dx_true = self.dx_true
             tau = _MPCQPStepped.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T,

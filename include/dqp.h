@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define DQP_VERSION 300 /* 0.3.0: DQP_FLAG_STRICT_GET_STEP, dqp_mpc_qp_forward_stepped (caller-supplied equality
+#define DQP_VERSION 301 /* 0.3.1: stage-wise MPC kernels for 16 < n_state + n_ctrl <= 32 (compiled pairs), same entry points;
+                           0.3.0: DQP_FLAG_STRICT_GET_STEP, dqp_mpc_qp_forward_stepped (caller-supplied equality
                            residual, one PDIPM iteration range per call), dqp_trace_begin / dqp_trace_end, DQP_MAX_DIM_LARGE
                            (blocked dense kernels above DQP_MAX_DIM);
                            0.2.1x: dqp_mpc_qp_backward takes C and F, dqp_mpc_dims.dyn_id, dqp_mpc_qp_termination_bytes,
@@ -264,10 +265,16 @@ int dqp_mpc_assemble_backward(const dqp_mpc_dims *dims, const double *dQ, const 
  * (dqp_mpc_qp_workspace_bytes).  Two kernel families serve it:
  *   - QP sizes with a null-space kernel (small horizons, nz <= 48): the whole QP lives in registers, the
  *     workspace carries the factorisation context from forward to backward (C, F unused by backward);
- *   - any other horizon with n_state + n_ctrl <= 16 and a compiled (n_state, n_ctrl) pair -- e.g.
+ *   - any other horizon with a compiled (n_state, n_ctrl) pair, n_state + n_ctrl <= 32 -- e.g.
  *     BASELINE config 4: n 12, m 4, T 30, nz 480 --: stage-wise PDIPM, every KKT solve a Riccati
  *     recursion over the knots (O(T (n+m)^3)); iterates and per-knot factors stream through the
- *     workspace; backward refactors at the returned iterate and needs C and F again.
+ *     workspace; backward refactors at the returned iterate and needs C and F again.  Pairs with
+ *     n + m <= 16 run four QPs per wavefront (one 16-lane DPP row each), the wide pairs (13, 4), (14, 7)
+ *     and (24, 8) two (one 32-lane half-wavefront each).
+ * Workspace of the stage-wise kernels, bytes: 8 * Bp * W with Bp = B rounded up to a multiple of 4
+ * (n + m <= 16) or of 2 (wide pairs), nt = n + m, ev(x) = x rounded up to even, and
+ *     W = ev(ev(ev(T (3 nt + 4 n + 14 m)) + T n^2) + T nt m + T (n + m))
+ * (dqp_mpc_qp_stepped_workspace_bytes: 8 * Bp * (W + 8)).
  * tau (B, T, n_state+n_ctrl) = the QP solution per knot [x_t, u_t]; lam/nu/slack/info/best_resid and
  * the termination modes as in dqp_qp_forward; backward = DenseQPFunction's (un-clamped d).
  */
@@ -299,7 +306,7 @@ int dqp_mpc_qp_backward(const dqp_mpc_dims *dims, const dqp_opts *opts, const do
  * call with it_end == opts->max_iter finishes as dqp_mpc_qp_forward does (batch rule included) and leaves the
  * returned best iterate and its multipliers in tau, lam, nu, slack.  All solver state between calls lives in
  * `workspace` (dqp_mpc_qp_stepped_workspace_bytes: always the caller's buffer) and `termination`.
- * Shapes: compiled (n_state, n_ctrl) pairs with n_state + n_ctrl <= 16.
+ * Shapes: the stage-wise pairs of dqp_mpc_qp_forward (compiled (n_state, n_ctrl), n_state + n_ctrl <= 32).
  */
 size_t dqp_mpc_qp_stepped_workspace_bytes(const dqp_mpc_dims *dims);
 size_t dqp_mpc_qp_stepped_termination_bytes(const dqp_mpc_dims *dims, const dqp_opts *opts);
