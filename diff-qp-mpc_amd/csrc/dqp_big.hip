@@ -897,6 +897,10 @@ __global__ __launch_bounds__(NTHR) void backward_kernel(KParams P)
     __syncthreads();
     kkt_wz(sm, ws, D, S.rxh, -1, S.rz, S.ry, S.dz);                  // dlam
     kkt_xy(sm, ws, D, S.rxh, S.ry, S.dz, S.dxh, S.te2);                   // dxh, dnu
+    // kkt_xy writes dxh[0..N) only; the L^-T sweep below reads all NP entries, and a zero row of Lq times whatever an
+    // earlier kernel left in that LDS (a NaN) is not zero
+    for (int i = N + tid; i < NP; i += NTHR) sm[S.dxh + i] = 0.0;
+    __syncthreads();
     trsv_LT(sm, S.dxh, C.Lq, NP, NP, C.Lqi, S.ct);                    // dx
     const LP dx = sm + S.dxh, dlam = sm + S.dz, dnu = sm + S.te2;
     for (int i = tid; i < N; i += NTHR) if (P.dp) P.dp[qp * N + i] = dx[i];

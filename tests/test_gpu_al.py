@@ -378,7 +378,7 @@ def test_config4_full_size_properties():
 
 @pytest.mark.parametrize("group", ["16", "8"])
 @pytest.mark.parametrize("robot,T", [("pendulum_euler", 20), ("cartpole1l", 20), ("cartpole2l", 5), ("pendulum_dx", 10),
-                                     ("pendulum1l", 3), ("rexquadrotor", 30), ("rexquadrotor", 4)])
+                                     ("pendulum1l", 3), ("rexquadrotor", 30), ("rexquadrotor", 4), ("cartpole2l", 12)])
 def test_banded_newton_step_vs_dense_oracle(robot, T, group, monkeypatch):
     """dqp_al_banded_newton_step (block-tridiagonal Cholesky, every knot in registers) against the
     reference's dense formulation restated in numpy (oracle/al_oracle.py: dense constraint Jacobian,

@@ -60,6 +60,33 @@ def test_big_vs_oracle(nz, nineq, neq, B, termination):
             np.testing.assert_allclose(t.cpu().numpy()[m], og["d" + k][m], err_msg="d%s (oracle point %s)" % (k, from_oracle), **GT)
 
 
+@pytest.mark.parametrize("nz,nineq,neq", [(100, 100, 0), (90, 90, 15)])
+def test_big_backward_ignores_stale_lds(nz, nineq, neq):
+    """The backward pads its x-direction to a multiple of 64 for the Lq^-T sweep, where a zero row of Lq meets the
+    padding: the padding has to be zeroed by the kernel, not taken from what LDS holds.  Between the forward and the
+    backward of this batch, a forward on NaN inputs at the same padded sizes (whose LDS vectors are NaN over their whole
+    length) runs on every CU; the gradients at the oracle's point must still be the oracle's."""
+    from diff_qp_mpc_amd import qp as qpmod
+    B = 6
+    ins_np = family(100 + nz + neq, B, nz, nineq, neq, "R")
+    o = oracle.qp_forward(*ins_np)
+    d = lambda a: dev(a, grad=False)
+    saved = qpmod._forward_impl(*[d(a) for a in ins_np], 1e-12, 20, 3, termination="per_problem")[-1]
+    pad = lambda k: -(-k // 64) * 64
+    Bp, NP, MP, EP = 512, pad(nz), pad(nineq), pad(neq) if neq else 0
+    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float64, device="cuda")
+    qpmod._forward_impl(nan(Bp, NP, NP), nan(Bp, NP), nan(Bp, MP, NP), nan(Bp, MP),
+                        nan(Bp, EP, NP) if EP else torch.empty(0, device="cuda", dtype=torch.float64),
+                        nan(Bp, EP) if EP else torch.empty(0, device="cuda", dtype=torch.float64),
+                        1e-12, 20, 3, termination="per_problem")
+    ct = np.random.default_rng(1).standard_normal((B, nz))
+    og = oracle.qp_backward(ins_np[0], ins_np[2], ins_np[4], o["zhat"], o["lam"], o["nu"], o["slack"], ct)
+    gr = qpmod._backward_impl(saved, d(o["zhat"]), d(o["lam"]), d(o["nu"]), d(o["slack"]), d(ct), (True,) * 6, 0)
+    for k, t in zip("QpGhAb", gr):
+        if t is not None:
+            np.testing.assert_allclose(t.cpu().numpy(), og["d" + k], err_msg="d" + k, **GT)
+
+
 def test_big_backward_without_context_and_dense_flag():
     """dqp_qp_backward without DQP_FLAG_BACKWARD_CTX rebuilds the factorisations from Q, G, A in its workspace; with
     DQP_FLAG_DENSE_BACKWARD d = lam / slack is not clamped (qp.py:246-250): both against the oracle."""
