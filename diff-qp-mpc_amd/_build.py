@@ -30,9 +30,16 @@ R16N_SIZES = [s for s in R16_SIZES if s[2] > 0] + [
     (35, 10, 30),   # n=6 m=1 T=5  (cartpole-2)
 ]
 
+# host-only stage-wise pairs (csrc/dqp_ric_host.hip; their union is DQP_RIC_HOST_SIZES of csrc/dqp_common.h), one
+# object per part: a wide pair alone takes ~30 s, so the parts compile side by side
+RIC_HOST_PARTS = [
+    [(15, 1), (14, 2), (13, 3), (11, 5)], [(10, 6), (9, 7), (8, 8)],
+    [(31, 1)], [(30, 2)], [(29, 3)], [(28, 4)], [(27, 5)], [(26, 6)], [(25, 7)],
+]
+
 PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip", "dqp_al_banded.hip",
-                 "dqp_ric.hip", "dqp_ric_wide.hip", "dqp_trace.hip", "dqp_big.hip"]
-SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip"]
+                 "dqp_ric.hip", "dqp_ric_wide.hip", "dqp_ric_pad.hip", "dqp_trace.hip", "dqp_big.hip"]
+SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric_host.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-MD",
          "-mllvm", "-pragma-unroll-threshold=10000000", "-mllvm", "-unroll-threshold=10000000"]
 
@@ -73,12 +80,19 @@ def _jobs():
     for src in PLAIN_SOURCES:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         jobs.append((obj, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]))
+    for k, pairs in enumerate(RIC_HOST_PARTS):
+        obj = os.path.join(CSRC, "dqp_ric_host%d.o" % k)
+        jobs.append((obj, [cc] + FLAGS + ["-DDQP_RIC_HOST_PART=%d" % k,
+                                          "-DDQP_RIC_HOST_PART_SIZES=" + " ".join("X(%d,%d)" % p for p in pairs),
+                                          "-c", os.path.join(CSRC, "dqp_ric_host.hip"), "-o", obj]))
     # longest compiles first (the 3-slot null-space forwards take ~4 min each, the metric-size
     # kernels ~2-3 min, everything else seconds): keeps the wall time near total CPU / cores
     def cost(j):
         name = os.path.basename(j[0])
         m = [int(t) for t in name.replace(".o", "").split("_")[-3:]] if name.count("_") >= 4 else None
         if m is None:
+            if "ric" in name and "pad" not in name:            # stage-wise kernels: ~2 min (dqp_ric), ~30-50 s the others
+                return 10 ** 5
             return 10 ** 9 if "pdipm" in name else 1          # the generic kernels: ~2 min
         n, mm, e = m
         w = n * n * (n + mm)

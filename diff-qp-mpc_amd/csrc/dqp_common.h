@@ -125,6 +125,39 @@ long long ricw_stepped_workspace_doubles(int n_state, int n_ctrl, int T, int B);
 int ricw_forward_stepped(const KParams &P, void *stream);
 int ricw_backward(const KParams &P, void *stream);
 int ricw_snapshot_doubles(int n_state, int n_ctrl, int T);
+// host-only pairs of the same kernels (dqp_ric_host.hip, one object per part of _build.RIC_HOST_PARTS): no dense route
+// or native stage-wise route changes because of them, they only run padded problems (dqp_mpc_dims.n_state_host)
+#define DQP_RIC_HOST16_SIZES X(15, 1) X(14, 2) X(13, 3) X(11, 5) X(10, 6) X(9, 7) X(8, 8)
+#define DQP_RIC_HOSTW_SIZES X(31, 1) X(30, 2) X(29, 3) X(28, 4) X(27, 5) X(26, 6) X(25, 7)
+#define DQP_RIC_HOST_SIZES DQP_RIC_HOST16_SIZES DQP_RIC_HOSTW_SIZES
+#define DQP_RIC_HOST_PART_IDS PART(0) PART(1) PART(2) PART(3) PART(4) PART(5) PART(6) PART(7) PART(8)
+enum { RIC_HOST_FORWARD = 0, RIC_HOST_STEPPED = 1, RIC_HOST_BACKWARD = 2 };
+#define PART(k) int ric_host_run_##k(int op, const KParams &P, void *stream);    // 1: not a pair of part k
+DQP_RIC_HOST_PART_IDS
+#undef PART
+// any stage-wise pair, native or host-only (dqp_ric_pad.hip): the same per-QP layout and snapshot in all families
+bool stage_supported(int n_state, int n_ctrl);
+bool stage_native(int n_state, int n_ctrl);                     // ric_supported || ricw_supported
+int stage_q(int n_state, int n_ctrl);                           // problems per wavefront: 4 (n + m <= 16) or 2
+long long stage_layout_doubles(int n_state, int n_ctrl, int T); // 0: no kernel for (n, m)
+int stage_forward(const KParams &P, void *stream);              // the linear-residual forward (no registered model)
+int stage_forward_stepped(const KParams &P, void *stream);
+int stage_backward(const KParams &P, void *stream);
+// Padded problems: a problem (n, m) on the kernels of (n', m), n' >= n, with n' - n dummy states after the real ones
+// (identity cost, zero dynamics rows, zero start).  Region of the caller's workspace behind the kernels' part:
+struct PadRegion {
+    double *C, *F, *c, *tau, *g, *dc, *f, *df, *nu, *ry, *x0, *dx0, *dC, *dF;
+};
+// the kernels' part in front of it: B rounded up to whole wavefronts times the per-QP workspace (stepped: plus the loop state)
+long long pad_kernel_doubles(int n_host, int n_ctrl, int T, int B, bool stepped);
+long long pad_region_doubles(int n_host, int n_ctrl, int T, int B);
+PadRegion pad_region(double *base, int n_host, int n_ctrl, int T, int B);
+// the copies (element-wise, coalesced, no host synchronisation); NULL arrays are skipped
+int pad_pack(int n, int n_host, int m, int T, int B, const PadRegion &R, const double *C, const double *c, const double *F,
+             const double *f, const double *x0, const double *tau, const double *nu, const double *g, const double *ry,
+             void *stream);
+int pad_unpack(int n, int n_host, int m, int T, int B, const PadRegion &R, double *tau, double *nu, double *dC, double *dc,
+               double *dF, double *df, double *dx0, void *stream);
 // dense QPs above DQP_MAX_DIM (dqp_big.hip): one QP per workgroup, matrices in the workspace, MFMA tiles
 long long big_workspace_doubles(int N, int M, int E);
 bool big_fits(int N, int M, int E);         // the solver's vectors fit the LDS of a CU

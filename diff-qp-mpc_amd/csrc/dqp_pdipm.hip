@@ -904,8 +904,10 @@ static int forward_once(const KParams &P, size_t lds, void *workspace, void *str
 // time-major MPC data and scatter the gradients back the same way -- no dense QP in HBM.
 // Which kernels serve an MPC shape: the dense null-space kernels where the QP size has an
 // instantiation (small horizons: one QP in registers), else the stage-wise Riccati kernels
-// (dqp_ric.hip: any horizon, n + m <= 16; dqp_ric_wide.hip: the same for 16 < n + m <= 32).
-enum { MPC_NONE = 0, MPC_R16N = 1, MPC_RIC = 2, MPC_RICW = 3 };
+// (dqp_ric.hip: any horizon, n + m <= 16; dqp_ric_wide.hip: the same for 16 < n + m <= 32).  MPC_PAD: the caller
+// names a host pair (dqp_mpc_dims.n_state_host), the problem runs padded with dummy states on its stage-wise kernels
+// (dqp_ric_pad.hip; the padded copies live in the caller's workspace behind the kernels' part).
+enum { MPC_NONE = 0, MPC_R16N = 1, MPC_RIC = 2, MPC_RICW = 3, MPC_PAD = 4 };
 
 // per-QP workspace of the stage-wise kernels (the same layout in both families); 0: no kernel for (n, m)
 static long long stage_ws_doubles(int n, int m, int T)
@@ -922,6 +924,18 @@ static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, 
     d.nz = md->T * (md->n_state + md->n_ctrl);
     d.nineq = 2 * md->T * md->n_ctrl;
     d.neq = md->T * md->n_state;
+    if (md->n_state_host) {     // a host pair: every registered model is native, no null-space route
+        const int np = md->n_state_host, m = md->n_ctrl;
+        if (md->dyn_id || np < md->n_state || !stage_supported(np, m)) return DQP_ERR_BAD_ARG;
+        if (md->T > 200000 || stage_layout_doubles(np, m, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
+        P.stamps = nullptr;
+        P.B = d.nbatch; P.N = md->T * (np + m); P.M = d.nineq; P.E = md->T * np;
+        fill_opts(opts, P);
+        P.dynId = 0; P.dynDt = 0.0;
+        P.mn = np; P.mm = m; P.mT = md->T;
+        kind = MPC_PAD;
+        return DQP_OK;
+    }
     if (md->dyn_id) {       // true-dynamics residual: a registered model of this size, stage-wise kernels
         int32_t dn = 0, dm = 0;
         if (dqp_dyn_sizes(md->dyn_id, &dn, &dm) != DQP_OK || dn != md->n_state || dm != md->n_ctrl) return DQP_ERR_BAD_ARG;
@@ -951,6 +965,7 @@ static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, 
 
 static size_t mpc_workspace_doubles(const KParams &P, int kind)
 {
+    if (kind == MPC_PAD) return (size_t)(pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false) + pad_region_doubles(P.mn, P.mm, P.mT, P.B));
     if (kind == MPC_R16N) return (size_t)P.B * (size_t)r16n_workspace_doubles(P.N, P.M, P.E);
     // four problems per wavefront (two for the wide pairs), padding rows own a slot too
     if (kind == MPC_RICW) return (size_t)((P.B + 1) / 2 * 2) * (size_t)ricw_workspace_doubles(P.mn, P.mm, P.mT);
@@ -959,6 +974,7 @@ static size_t mpc_workspace_doubles(const KParams &P, int kind)
 
 static int mpc_snapshot_doubles(const KParams &P, int kind)
 {
+    if (kind == MPC_PAD) return P.mT * (2 * P.mn + 5 * P.mm);      // the stage-wise snapshot of the host pair
     if (kind == MPC_RICW) return ricw_snapshot_doubles(P.mn, P.mm, P.mT);
     return kind == MPC_R16N ? r16n_snapshot_doubles(P.N, P.M, P.E) : ric_snapshot_doubles(P.mn, P.mm, P.mT);
 }
@@ -1005,38 +1021,59 @@ dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C
         return DQP_ERR_BAD_ARG;
     if (P.dynId && !(P.dynDt > 0.0)) return DQP_ERR_BAD_ARG;        // the model's step needs dqp_opts.dyn_dt
     auto run = [&](const KParams &Q) {
+        if (kind == MPC_PAD) return stage_forward(Q, stream);
         return kind == MPC_R16N ? r16n_forward(Q, stream) : kind == MPC_RICW ? ricw_forward(Q, stream) : ric_forward(Q, stream);
     };
     P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0; P.mul = u_lower; P.muu = u_upper;
     P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
     P.workspace = (double *)workspace;
     if (P.maxIter < 1) return DQP_ERR_BAD_ARG;
-    if (!(P.flags & DQP_FLAG_BATCH_TERMINATION)) return run(P);
-    if (!termination || P.maxIter > 64) return DQP_ERR_BAD_ARG;
+    const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
+    if (batch && (!termination || P.maxIter > 64)) return DQP_ERR_BAD_ARG;
+    // padded: the host kernels read the padded copies and write tau, nu padded (lam, slack have the caller's layout)
+    PadRegion R = {};
+    if (kind == MPC_PAD) {
+        R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false), P.mn, P.mm, P.mT, P.B);
+        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, C, c, F, f, x0, nullptr, nullptr, nullptr, nullptr, stream);
+        if (rc != DQP_OK) return rc;
+        P.mC = R.C; P.mc = R.c; P.mF = R.F; P.mf = R.f; P.mx0 = R.x0; P.zhat = R.tau; P.nu = R.nu;
+    }
+    auto done = [&](int r) {
+        if (r != DQP_OK || kind != MPC_PAD) return r;
+        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, tau, nu, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    };
+    if (!batch) return done(run(P));
     P.eps = opts ? opts->eps : 1e-12;
     term_bind_pass1(P, termination, mpc_snapshot_doubles(P, kind));
     if ((rc = run(P)) != DQP_OK) return rc;
-    if (P.flags & DQP_FLAG_HISTORY_ONLY) return DQP_OK;
+    if (P.flags & DQP_FLAG_HISTORY_ONLY) return done(DQP_OK);
     if ((rc = term_decide(P, termination, stream)) != DQP_OK) return rc;
     term_bind_pass2(P, termination);
-    return kind == MPC_R16N ? r16n_forward(P, stream) : ric_finish(P, stream);
+    return done(kind == MPC_R16N ? r16n_forward(P, stream) : ric_finish(P, stream));
 }
 
 static int stage_snapshot_doubles(int n, int m, int T)
 {
-    return ric_supported(n, m) ? ric_snapshot_doubles(n, m, T) : ricw_snapshot_doubles(n, m, T);
+    return stage_supported(n, m) ? T * (2 * n + 5 * m) : 0;        // ric_snapshot_doubles of every stage-wise pair
 }
 
-// the stage-wise kernels only, whatever the horizon (the null-space kernels keep their iterate in registers)
+// the stage-wise kernels only, whatever the horizon (the null-space kernels keep their iterate in registers); with
+// n_state_host the kernels of (n_state_host, n_ctrl) on the padded problem (P.mn is then the host's state count)
 static int stepped_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P)
 {
     if (!md || md->nbatch < 0 || md->n_state <= 0 || md->n_ctrl <= 0 || md->T < 2 || !md->has_bounds) return DQP_ERR_BAD_ARG;
-    if (!ric_supported(md->n_state, md->n_ctrl) && !ricw_supported(md->n_state, md->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    if (md->T > 200000 || stage_ws_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
+    int np = md->n_state;
+    if (md->n_state_host) {
+        np = md->n_state_host;
+        if (md->dyn_id || np < md->n_state || !stage_supported(np, md->n_ctrl)) return DQP_ERR_BAD_ARG;
+    } else if (!ric_supported(md->n_state, md->n_ctrl) && !ricw_supported(md->n_state, md->n_ctrl)) {
+        return DQP_ERR_TOO_LARGE;
+    }
+    if (md->T > 200000 || stage_layout_doubles(np, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
     P.B = md->nbatch;
-    P.N = md->T * (md->n_state + md->n_ctrl); P.M = 2 * md->T * md->n_ctrl; P.E = md->T * md->n_state;
+    P.N = md->T * (np + md->n_ctrl); P.M = 2 * md->T * md->n_ctrl; P.E = md->T * np;
     fill_opts(opts, P);
-    P.mn = md->n_state; P.mm = md->n_ctrl; P.mT = md->T;
+    P.mn = np; P.mm = md->n_ctrl; P.mT = md->T;
     return DQP_OK;
 }
 
@@ -1044,6 +1081,8 @@ __attribute__((visibility("default"))) size_t dqp_mpc_qp_stepped_workspace_bytes
 {
     KParams P = {};
     if (stepped_params(md, nullptr, P) != DQP_OK || md->nbatch <= 0) return 0;
+    if (md->n_state_host)
+        return (size_t)(pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, true) + pad_region_doubles(P.mn, P.mm, P.mT, P.B)) * sizeof(double);
     const long long n = ric_supported(P.mn, P.mm) ? ric_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B)
                                                   : ricw_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B);
     return (size_t)n * sizeof(double);
@@ -1077,17 +1116,36 @@ dqp_mpc_qp_forward_stepped(const dqp_mpc_dims *md, const dqp_opts *opts, const d
     P.workspace = (double *)workspace;
     P.extRy = ext_ry; P.itBegin = it_begin; P.itEnd = it_end;
     const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
+    if (batch && (!termination || P.maxIter > 64)) return DQP_ERR_BAD_ARG;
+    // padded: the call that starts the solve packs the problem, the later ones reuse that copy; every call pads
+    // ext_ry and hands the caller the compact iterate (and the compact nu with the final one)
+    const bool pad = md->n_state_host != 0;
+    PadRegion R = {};
+    if (pad) {
+        R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, true), P.mn, P.mm, P.mT, P.B);
+        const bool first = it_begin == 0;
+        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, first ? C : nullptr, first ? c : nullptr, first ? F : nullptr,
+                      first ? f : nullptr, first ? x0 : nullptr, nullptr, nullptr, nullptr, it_end > it_begin ? ext_ry : nullptr,
+                      stream);
+        if (rc != DQP_OK) return rc;
+        P.mC = R.C; P.mc = R.c; P.mF = R.F; P.mf = R.f; P.mx0 = R.x0; P.zhat = R.tau; P.nu = R.nu;
+        P.extRy = it_end > it_begin ? R.ry : nullptr;
+    }
+    auto done = [&](int r) {
+        if (r != DQP_OK || !pad) return r;
+        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, tau, it_end == P.maxIter ? nu : nullptr, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, stream);
+    };
     if (batch) {
-        if (!termination || P.maxIter > 64) return DQP_ERR_BAD_ARG;
         P.eps = opts ? opts->eps : 1e-12;
         term_bind_pass1(P, termination, stage_snapshot_doubles(P.mn, P.mm, P.mT));
     }
-    rc = ric_supported(P.mn, P.mm) ? ric_forward_stepped(P, stream) : ricw_forward_stepped(P, stream);
+    rc = pad ? stage_forward_stepped(P, stream) : ric_supported(P.mn, P.mm) ? ric_forward_stepped(P, stream) : ricw_forward_stepped(P, stream);
     if (rc != DQP_OK) return rc == 1 ? DQP_ERR_TOO_LARGE : rc;
-    if (it_end < P.maxIter || !batch || (P.flags & DQP_FLAG_HISTORY_ONLY)) return DQP_OK;
+    if (it_end < P.maxIter || !batch || (P.flags & DQP_FLAG_HISTORY_ONLY)) return done(DQP_OK);
     if ((rc = term_decide(P, termination, stream)) != DQP_OK) return rc;
     term_bind_pass2(P, termination);
-    return ric_finish(P, stream);
+    return done(ric_finish(P, stream));
 }
 
 __attribute__((visibility("default"))) int
@@ -1111,7 +1169,26 @@ dqp_mpc_qp_backward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *
     if (kind == MPC_R16N) return r16n_backward(P, stream);
     if (!C || !F) return DQP_ERR_BAD_ARG;
     P.mC = C; P.mF = F;
+    if (kind == MPC_PAD) {      // re-padded inputs (their dummy entries are exactly zero), padded gradients, compact copies
+        const PadRegion R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false), P.mn, P.mm, P.mT, P.B);
+        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, C, nullptr, F, nullptr, nullptr, tau, nu, dl_dtau, nullptr, stream);
+        if (rc != DQP_OK) return rc;
+        P.mC = R.C; P.mF = R.F; P.zin = R.tau; P.nuin = R.nu; P.gin = R.g;
+        P.mdC = dC ? R.dC : nullptr; P.mdc = dc ? R.dc : nullptr; P.mdF = dF ? R.dF : nullptr;
+        P.mdf = df ? R.df : nullptr; P.mdx0 = dx0 ? R.dx0 : nullptr;
+        if ((rc = stage_backward(P, stream)) != DQP_OK) return rc;
+        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, nullptr, nullptr, dC, dc, dF, df, dx0, stream);
+    }
     return kind == MPC_RICW ? ricw_backward(P, stream) : ric_backward(P, stream);
+}
+
+// the smallest compiled stage-wise pair (n', n_ctrl), n' >= n_state, native or host-only; 0: none
+__attribute__((visibility("default"))) int32_t dqp_mpc_qp_host_n_state(const dqp_mpc_dims *md)
+{
+    if (!md || md->n_state < 1 || md->n_ctrl < 1 || !md->has_bounds || md->dyn_id) return 0;
+    for (int np = md->n_state; np + md->n_ctrl <= 32; ++np)     // ascending n': the 16-lane pairs come first
+        if (stage_supported(np, md->n_ctrl)) return np;
+    return 0;
 }
 
 __attribute__((visibility("default"))) int

@@ -81,6 +81,11 @@ template <int G> __device__ __forceinline__ double gmin(double v)
     return fmin(a, b);
 }
 
+// the 16-lane host-only pairs (dqp_ric_host.hip, DQP_RIC_HOST16_SIZES of dqp_common.h)
+#define X(a, b) (n == a && m == b) ||
+constexpr bool host16_pair(int n, int m) { return DQP_RIC_HOST16_SIZES false; }
+#undef X
+
 // WSL: the per-QP workspace (iterates, directions, factors) lives in LDS instead of the caller's buffer --
 // the forward kernel of short horizons, where it fits beside the stage and a knot step is latency, not bandwidth
 template <int NX_, int NU_, bool WSL_ = false> struct Cfg {
@@ -92,6 +97,9 @@ template <int NX_, int NU_, bool WSL_ = false> struct Cfg {
     static constexpr int WPE = G == 16 ? DQP_RIC_WPE : 1;      // the wide knot needs the whole register file
     static_assert(NT <= 32, "a knot must fit a 32-lane half-wavefront");
     static_assert(G == 16 || !WSL, "no LDS-resident workspace for the wide knot");
+    // the stage's LDS addresses through an integer (Img::lds_ptr): two problems per wavefront, and the 16-lane
+    // host pairs, where the plain cast hits the same compiler error (the native 16-lane pairs keep the cast)
+    static constexpr bool INT_LDS = Q != 4 || host16_pair(NX_, NU_);
 };
 
 // per-QP workspace (doubles); everything knot-major
@@ -186,7 +194,7 @@ __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::
 __device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // one kind of matrix in the stage: rows of RL doubles, Q problems
-template <int RL, int Q = 4> struct Img {
+template <int RL, int Q = 4, bool INT_LDS = (Q != 4)> struct Img {
     static constexpr int PIECE = (RL % 2 == 0) ? 16 : 4;            // bytes per lane of one DMA instruction
     static constexpr int PPR = RL * 8 / PIECE;                       // pieces per matrix row
     // rows of 2^k 16-byte pieces start on few distinct bank groups: piece j of row `row` sits at j ^ swz(row)
@@ -231,11 +239,12 @@ template <int RL, int Q = 4> struct Img {
             else out[i] = img[root + i * RL];
         }
     }
-    // the LDS address of a pointer into the stage.  Q = 2 takes it through an integer: there this compiler
-    // folds the plain cast's null check into an illegal `v_cmp_ne_u32 0, src_shared_base` and stops
+    // the LDS address of a pointer into the stage.  INT_LDS takes it through an integer: there this compiler
+    // folds the plain cast's null check into an illegal `v_cmp_ne_u32 0, src_shared_base` and stops (Q = 2, and
+    // 16-lane host pairs such as (15, 1); Cfg::INT_LDS)
     __device__ __forceinline__ static lvoid_t *lds_ptr(double *p)
     {
-        if constexpr (Q == 4) return (lvoid_t *)p;
+        if constexpr (!INT_LDS) return (lvoid_t *)p;
         else return (lvoid_t *)(uintptr_t)(uint32_t)(uintptr_t)p;
     }
     // issue the DMA of one knot's ROWS x RL matrices: place q's matrix is at base + min(q, qmax) * qstride_bytes
@@ -281,10 +290,10 @@ template <int RL, int Q = 4> struct Img {
 // the wavefront's image: [C_t | F_t] while factorising, [P_t | L_t | F_t] in the vector sweeps
 template <class C> struct Stage {
     static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
-    using MC = Img<NT, C::Q>;       // C_t: NT rows of NT
-    using MF = Img<NT, C::Q>;       // F_t: NX rows of NT
-    using MP = Img<NX, C::Q>;       // cost-to-go P_t: NX rows of NX
-    using ML = Img<NU, C::Q>;       // [Lxu ; Luu] with 1 / L_jj on the diagonal: NT rows of NU
+    using MC = Img<NT, C::Q, C::INT_LDS>;       // C_t: NT rows of NT
+    using MF = Img<NT, C::Q, C::INT_LDS>;       // F_t: NX rows of NT
+    using MP = Img<NX, C::Q, C::INT_LDS>;       // cost-to-go P_t: NX rows of NX
+    using ML = Img<NU, C::Q, C::INT_LDS>;       // [Lxu ; Luu] with 1 / L_jj on the diagonal: NT rows of NU
     static constexpr int OL = MP::doubles(NX);
     static constexpr int OF = MC::doubles(NT) > OL + ML::doubles(NT) ? MC::doubles(NT) : OL + ML::doubles(NT);
     static constexpr int TOTAL = OF + MF::doubles(NX);

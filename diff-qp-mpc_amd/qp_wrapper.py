@@ -142,7 +142,8 @@ class _MPCQP(Function):
     solve through dqp_mpc_qp_forward -- the dense (Q,p,G,h,A,b) exists only in registers -- and
     the backward straight into (dC, dc, dF, df, dx0) (dqp_mpc_qp_backward).  Shapes: small horizons on the
     null-space kernels, any horizon on the stage-wise ones for a compiled (n_state, n_ctrl) pair with
-    n_state + n_ctrl <= 32 (supported() asks the library)."""
+    n_state + n_ctrl <= 32 (supported() asks the library).  n_state_host != 0: the stage-wise kernels of the pair
+    (n_state_host, n_ctrl) on the problem padded with dummy states (host_n_state(): any n_ctrl <= 8, n + m <= 32)."""
 
     @staticmethod
     def supported(B, n_state, n_ctrl, T, dyn=None):
@@ -150,7 +151,16 @@ class _MPCQP(Function):
         return bool(_lib.load().dqp_mpc_qp_supported(ctypes.byref(dims)))
 
     @staticmethod
-    def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T, dyn=None):
+    def host_n_state(B, n_state, n_ctrl, T):
+        """The smallest compiled stage-wise host (n', n_ctrl), n' >= n_state, that takes this problem padded; 0: none."""
+        lib = _lib.load()
+        nh = int(lib.dqp_mpc_qp_host_n_state(ctypes.byref(_lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0))))
+        if nh and lib.dqp_mpc_qp_supported(ctypes.byref(_lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0, nh))):
+            return nh
+        return 0
+
+    @staticmethod
+    def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T, dyn=None, n_state_host=0):
         from . import qp as qpmod
         lib = _lib.load()
         for t in (C, c, F, f, x0):
@@ -164,7 +174,7 @@ class _MPCQP(Function):
             raise RuntimeError("u_lower/u_upper must have shape (n_ctrl,) (qp_wrapper.py:677-678)")
         # dyn: a DeviceDynamics whose true step is the equality residual of the iterations (the reference's
         # dyn_res closure, qp_wrapper.py:309,316); F, f stay the linearisation the Newton steps use
-        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, dyn.id if dyn is not None else 0)
+        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, dyn.id if dyn is not None else 0, n_state_host)
         batch = qpmod.TERMINATION == "batch"
         opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, 20, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
         if dyn is not None:
@@ -206,7 +216,7 @@ class _MPCQP(Function):
                                          ctypes.c_void_p(0), _ptr(ctx.ws), _stream(dev))
         _lib.check(rc, "dqp_mpc_qp_backward")
         outs = [None if o is None else o.to(ctx.dtype) for o in outs]
-        return (*outs, None, None, None, None, None, None)
+        return (*outs, None, None, None, None, None, None, None)
 
 
 class _MPCQPStepped(Function):
@@ -214,12 +224,24 @@ class _MPCQPStepped(Function):
     dyn_res closure once per PDIPM iteration on the current iterate (qp_wrapper.py:309,316 -> batch_LU.py:97).
     Here: one stage-wise PDIPM iteration per C-ABI call (dqp_mpc_qp_forward_stepped), the module evaluated in
     between on the iterate the call hands back -- one torch evaluation per iteration, everything else on chip.
-    Shapes: the stage-wise pairs, compiled (n_state, n_ctrl) with n_state + n_ctrl <= 32."""
+    Shapes: the stage-wise pairs, compiled (n_state, n_ctrl) with n_state + n_ctrl <= 32; any other n_ctrl <= 8,
+    n_state + n_ctrl <= 32 padded with dummy states onto the smallest compiled host (n', n_ctrl) (host_n_state()).
+    The residual callback sees the compact iterate either way."""
 
     @staticmethod
     def supported(B, n_state, n_ctrl, T):
         dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0)
         return int(_lib.load().dqp_mpc_qp_stepped_workspace_bytes(ctypes.byref(dims))) > 0
+
+    @staticmethod
+    def host_n_state(B, n_state, n_ctrl, T):
+        """0 where the native pair serves, else the host the library names for the padded problem (-1: none)."""
+        if _MPCQPStepped.supported(B, n_state, n_ctrl, T):
+            return 0
+        lib = _lib.load()
+        nh = int(lib.dqp_mpc_qp_host_n_state(ctypes.byref(_lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0))))
+        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0, nh)
+        return nh if nh and int(lib.dqp_mpc_qp_stepped_workspace_bytes(ctypes.byref(dims))) > 0 else -1
 
     @staticmethod
     def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T, residual):
@@ -230,7 +252,10 @@ class _MPCQPStepped(Function):
         keep = [cv(C), cv(c), cv(F), cv(f), cv(x0), cv(u_lower).reshape(-1), cv(u_upper).reshape(-1)]
         if keep[5].numel() != n_ctrl or keep[6].numel() != n_ctrl:
             raise RuntimeError("u_lower/u_upper must have shape (n_ctrl,) (qp_wrapper.py:677-678)")
-        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0)
+        nh = _MPCQPStepped.host_n_state(B, n_state, n_ctrl, T)
+        if nh < 0:
+            raise NotImplementedError("no stage-wise kernels for (n_state, n_ctrl) = (%d, %d)" % (n_state, n_ctrl))
+        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0, nh)
         batch = qpmod.TERMINATION == "batch"
         max_iter = 20
         opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, max_iter, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
@@ -446,11 +471,12 @@ class MPC(Module):
             # a caller's dynamics module: its residual is evaluated by torch once per PDIPM iteration, the iteration
             # itself runs on the stage-wise kernels (dqp_mpc_qp_forward_stepped)
             if (self.add_goal_constraint or ul is None
-                    or not _MPCQPStepped.supported(self.n_batch, self.n_state, self.n_ctrl, self.T)):
+                    or _MPCQPStepped.host_n_state(self.n_batch, self.n_state, self.n_ctrl, self.T) < 0):
                 raise NotImplementedError(
                     "qp_wrapper.MPC with a caller-supplied dynamics module evaluates the module's residual once per "
-                    "QP iteration (reference qp_wrapper.py:309,316) around the stage-wise kernels: that needs control "
-                    "bounds, no goal constraint and a compiled (n_state, n_ctrl) pair with n_state + n_ctrl <= 32.  "
+                    "QP iteration (reference qp_wrapper.py:309,316) around the stage-wise kernels (padded with dummy "
+                    "states where (n_state, n_ctrl) has no kernels of its own): that needs control bounds, no goal "
+                    "constraint, n_ctrl <= 8 and n_state + n_ctrl <= 32.  "
                     "Register the model (dynamics.DeviceDynamics) or pass linearised_residual=True otherwise.")
             dx_true = self.dx_true
             tau = _MPCQPStepped.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T,
@@ -466,6 +492,16 @@ class MPC(Module):
             tau = _MPCQP.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T, dyn_model)
             x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
             return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
+        nz = self.T * (self.n_state + self.n_ctrl)
+        if (dyn_res is None and not self.add_goal_constraint and ul is not None
+                and max(nz, 2 * self.T * self.n_ctrl, self.T * self.n_state) > _lib.DQP_MAX_DIM_LARGE):
+            # no kernel of its own and too large for the dense route: the stage-wise kernels of the smallest compiled
+            # host (n', n_ctrl), the problem padded with n' - n_state dummy states (exact; dqp_mpc_dims.n_state_host)
+            nh = _MPCQP.host_n_state(self.n_batch, self.n_state, self.n_ctrl, self.T)
+            if nh:
+                tau = _MPCQP.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T, None, nh)
+                x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
+                return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
         Q, q, G, h, A, b = _AssembleDenseQP.apply(cost.C, cost.c, F, f, x0, ul, uu,
                                                   self.n_state, self.n_ctrl, self.T)
         if self.add_goal_constraint:

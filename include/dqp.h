@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define DQP_VERSION 301 /* 0.3.1: stage-wise MPC kernels for 16 < n_state + n_ctrl <= 32 (compiled pairs), same entry points;
+#define DQP_VERSION 302 /* 0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
+                           0.3.1: stage-wise MPC kernels for 16 < n_state + n_ctrl <= 32 (compiled pairs), same entry points;
                            0.3.0: DQP_FLAG_STRICT_GET_STEP, dqp_mpc_qp_forward_stepped (caller-supplied equality
                            residual, one PDIPM iteration range per call), dqp_trace_begin / dqp_trace_end, DQP_MAX_DIM_LARGE
                            (blocked dense kernels above DQP_MAX_DIM);
@@ -231,6 +232,10 @@ typedef struct dqp_mpc_dims {
                              F tau + f in the equality residual of the PDIPM iterations -- the
                              reference's dyn_res closure (qp_wrapper.py:309,316); step = dqp_opts.dyn_dt.
                              Served by the stage-wise kernels.  Ignored by dqp_mpc_assemble etc.       */
+    int32_t n_state_host; /* dqp_mpc_qp_*: 0 (the routes below), or n' >= n_state with a compiled stage-wise pair
+                             (n', n_ctrl) (dqp_mpc_qp_host_n_state): the problem runs on that pair's kernels
+                             with n' - n_state dummy states, exactly (see "Padded problems" below).  Needs
+                             dyn_id == 0.  Ignored by dqp_mpc_assemble, _line_search, _rollout_backward.      */
 } dqp_mpc_dims;
 
 /*
@@ -275,11 +280,25 @@ int dqp_mpc_assemble_backward(const dqp_mpc_dims *dims, const double *dQ, const 
  * (n + m <= 16) or of 2 (wide pairs), nt = n + m, ev(x) = x rounded up to even, and
  *     W = ev(ev(ev(T (3 nt + 4 n + 14 m)) + T n^2) + T nt m + T (n + m))
  * (dqp_mpc_qp_stepped_workspace_bytes: 8 * Bp * (W + 8)).
+ * Padded problems (n_state_host = n' != 0): the kernels of the pair (n', m) -- native, or one of the host-only pairs
+ * (15,1) (14,2) (13,3) (11,5) (10,6) (9,7) (8,8) (31,1) (30,2) (29,3) (28,4) (27,5) (26,6) (25,7) -- solve the problem
+ * with d = n' - n dummy states after the real ones in every knot: identity cost and zero linear cost on them, zero
+ * dynamics rows, zero start.  Every Newton system is then block-diagonal in (real, dummy), so the iterates, stop
+ * iteration and gradients are those of the (n, m) problem up to round-off; the null-space route is never taken.
+ * Caller arrays keep the compact (n, m) shapes.  Workspace bytes: 8 * (Bp' * W' + R) with W' = W at (n', m), Bp' = B
+ * rounded up as for that pair (stepped: Bp' * (W' + 8)), nt' = n' + m, and the padded copies
+ *     R = 2 (ev(T B nt'^2) + ev((T-1) B n' nt') + 2 ev(T B nt') + ev(T B n') + ev((T-1) B n') + ev(B n')).
+ * Bad arguments: n' < n, (n', m) not compiled, dyn_id != 0.  The stepped call with it_begin == 0 copies C, c, F, f, x0
+ * into the workspace; the later calls of the solve read that copy.
  * tau (B, T, n_state+n_ctrl) = the QP solution per knot [x_t, u_t]; lam/nu/slack/info/best_resid and
  * the termination modes as in dqp_qp_forward; backward = DenseQPFunction's (un-clamped d).
  */
 int dqp_mpc_qp_supported(const dqp_mpc_dims *dims);
 size_t dqp_mpc_qp_workspace_bytes(const dqp_mpc_dims *dims);
+/* the smallest n' >= n_state with a compiled stage-wise pair (n', n_ctrl), native or host-only (ascending n': the 16-lane
+ * pairs before the wide ones), or 0 if there is none (n_ctrl > 8, n_state + n_ctrl > 32); needs has_bounds and
+ * dyn_id == 0, ignores n_state_host, T and nbatch */
+int32_t dqp_mpc_qp_host_n_state(const dqp_mpc_dims *dims);
 /* the `termination` buffer of dqp_mpc_qp_forward under DQP_FLAG_BATCH_TERMINATION (history, best-iteration list and the
  * improving iterates of pass 1, from which pass 2 finishes without solving again); 0 without the flag */
 size_t dqp_mpc_qp_termination_bytes(const dqp_mpc_dims *dims, const dqp_opts *opts);

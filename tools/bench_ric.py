@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Timing of the stage-wise MPC QP kernels (csrc/dqp_ric.hip) at the BASELINE config-4 shape:
 n_state 12, n_ctrl 4, T 30 (nz 480, nineq 240, neq 360), B = 8192 (BATCH), HIP events around the
-C-ABI calls dqp_mpc_qp_forward / dqp_mpc_qp_backward, both termination modes."""
+C-ABI calls dqp_mpc_qp_forward / dqp_mpc_qp_backward, both termination modes.
+HOST=n': the problem padded onto the kernels of (n', m) (dqp_mpc_dims.n_state_host), with the per-kernel split of one
+forward and backward (pack / solve / unpack).  DENSE=1: also assemble + DenseQPFunction on the same data (forward and
+backward, per-problem termination), the route the dense kernels give where nz <= 512."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -20,7 +23,8 @@ F = torch.cat([torch.eye(n, dtype=torch.float64, device="cuda") + 0.05 * rnd(T -
 f = 0.1 * rnd(T - 1, B, n)
 x0 = rnd(B, n)
 lo, hi = torch.full((m,), -0.4, dtype=torch.float64, device="cuda"), torch.full((m,), 0.4, dtype=torch.float64, device="cuda")
-dims = _lib.dqp_mpc_dims(B, n, m, T, 1, 0)
+host = int(os.environ.get("HOST", 0))
+dims = _lib.dqp_mpc_dims(B, n, m, T, 1, 0, host)
 assert lib.dqp_mpc_qp_supported(ctypes.byref(dims)) == 1
 kw = dict(dtype=torch.float64, device="cuda")
 tau = torch.empty(B, T, nt, **kw); lam = torch.empty(B, 2 * T * m, **kw); slack = torch.empty(B, 2 * T * m, **kw)
@@ -62,3 +66,26 @@ def bwd():
     assert rc == 0, rc
 tb_ = timed(bwd)
 print("backward %.2f ms" % tb_)
+
+if host:
+    opts = _lib.dqp_opts(1e-12, 1e-10, 20, 3, 0, 0)
+    with _lib.trace(64) as tr:
+        assert lib.dqp_mpc_qp_forward(ctypes.byref(dims), ctypes.byref(opts), P(C), P(c), P(F), P(f), P(x0), P(lo), P(hi),
+                                      P(tau), P(lam), P(nu), P(slack), P(info), P(resid), P(ws), None, None) == 0
+        bwd()
+        torch.cuda.synchronize()
+    for k, (cnt, ms) in tr.by_kernel().items():
+        print("  %-90s x%d  %.3f ms" % (k[:90], cnt, ms))
+if os.environ.get("DENSE"):
+    from diff_qp_mpc_amd import qp as qpmod, qp_wrapper
+    qpmod.TERMINATION = "per_problem"
+    ins = [t.detach().clone().requires_grad_() for t in (C, c, F, f, x0)]
+    def dense():
+        Q, p, G, h, A, b = qp_wrapper._AssembleDenseQP.apply(*ins, lo, hi, n, m, T)
+        z = qpmod.DenseQPFunction(verbose=-1)(Q, p, G, h, A, b)
+        z.sum().backward()
+    def padded():
+        z = qp_wrapper._MPCQP.apply(*ins, lo, hi, n, m, T, None, host)
+        z.sum().backward()
+    print("per problem, forward + backward through autograd: assemble + dense %.2f ms, padded stage-wise (host %d) %.2f ms"
+          % (timed(dense), host, timed(padded)))
