@@ -38,7 +38,7 @@ RIC_HOST_PARTS = [
 ]
 
 PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip", "dqp_al_banded.hip",
-                 "dqp_ric.hip", "dqp_ric_wide.hip", "dqp_ric_pad.hip", "dqp_trace.hip", "dqp_big.hip"]
+                 "dqp_al_banded_wide.hip", "dqp_ric.hip", "dqp_ric_wide.hip", "dqp_ric_pad.hip", "dqp_trace.hip", "dqp_big.hip"]
 SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric_host.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-MD",
          "-mllvm", "-pragma-unroll-threshold=10000000", "-mllvm", "-unroll-threshold=10000000"]
@@ -93,6 +93,8 @@ def _jobs():
         if m is None:
             if "ric" in name and "pad" not in name:            # stage-wise kernels: ~2 min (dqp_ric), ~30-50 s the others
                 return 10 ** 5
+            if "banded_wide" in name:                          # three wide pairs in one object: ~6 min
+                return 10 ** 9
             return 10 ** 9 if "pdipm" in name else 1          # the generic kernels: ~2 min
         n, mm, e = m
         w = n * n * (n + mm)

@@ -50,7 +50,7 @@ SYMBOLS = ("dqp_version", "dqp_error_string", "dqp_workspace_bytes", "dqp_termin
            "dqp_al_newton_step", "dqp_al_chol_solve", "dqp_al_assemble", "dqp_al_merit",
            "dqp_al_newton_solve_bytes", "dqp_al_newton_solve",
            "dqp_al_outer_update", "dqp_al_banded_factor_bytes", "dqp_al_banded_newton_step", "dqp_al_banded_solve",
-           "dqp_al_banded_newton_step_jac", "dqp_al_lane_group", "dqp_al_mpc_solve_bytes", "dqp_al_mpc_solve",
+           "dqp_al_banded_newton_step_jac", "dqp_al_banded_jac_factor_bytes", "dqp_al_lane_group", "dqp_al_mpc_solve_bytes", "dqp_al_mpc_solve",
            "dqp_mpc_qp_stepped_workspace_bytes", "dqp_mpc_qp_stepped_termination_bytes", "dqp_mpc_qp_forward_stepped", "dqp_trace_begin", "dqp_trace_end",
            "dqp_dyn_sizes", "dqp_dyn_step", "dqp_dyn_jacobian", "dqp_dyn_forward_dynamics",
            "dqp_dyn_forward_derivatives")
@@ -154,6 +154,8 @@ def load():
     lib.dqp_al_outer_update.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 12
     lib.dqp_al_banded_factor_bytes.restype = ctypes.c_size_t
     lib.dqp_al_banded_factor_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int]
+    lib.dqp_al_banded_jac_factor_bytes.restype = ctypes.c_size_t
+    lib.dqp_al_banded_jac_factor_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)]
     lib.dqp_al_banded_newton_step.restype = ctypes.c_int
     lib.dqp_al_banded_newton_step.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 12
     lib.dqp_al_banded_newton_step_jac.restype = ctypes.c_int

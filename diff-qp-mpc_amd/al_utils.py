@@ -393,9 +393,10 @@ class NewtonAL(torch.autograd.Function):
 
 
 def banded_jac_supported(B, n, m, T):
-    """A block-tridiagonal Newton step exists for caller-linearised dynamics of these sizes."""
+    """A block-tridiagonal Newton step exists for caller-linearised dynamics of these sizes (n + m <= 16: 8- / 16-lane
+    kernels; the wide pairs up to n + m = 32: one problem per half-wavefront)."""
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
-    return int(_lib.load().dqp_al_banded_factor_bytes(ctypes.byref(dims), 0)) > 0
+    return int(_lib.load().dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) > 0
 
 
 class NewtonALBandedJac(torch.autograd.Function):
@@ -417,7 +418,7 @@ class NewtonALBandedJac(torch.autograd.Function):
         dims = _lib.dqp_al_mpc_dims(B, n, m, T)
         rho_t = rho if torch.is_tensor(rho) else torch.full((B,), float(rho), **kw)
         keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho_t).reshape(B), d64(u_lower).reshape(-1), d64(u_upper).reshape(-1)]
-        fac = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), 0)) // 8, **kw)
+        fac = torch.empty(int(lib.dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) // 8, **kw)
         upd = torch.empty(B, T, nt, **kw)
         info = torch.empty(B, dtype=torch.int32, device=dev)
         x_est = xi

@@ -29,6 +29,10 @@
 // HBM per Newton step and problem: xu, Qd, q (3 nz) + lam (ncon) in, update (nz) + banded factor
 // (T (nt^2 + nt n + nt)) out -- e.g. 6.6 KB at cartpole T = 20 against 177 KB for the dense path
 // (Jc written + read, L written).
+//
+// Knots of 17 to 32 variables (caller-linearised dynamics only: DQP_BAND_WIDE_SIZES) take a 32-lane half-wavefront, two
+// problems per wavefront, rows over the lanes as above (Grp<32>); their instantiations are in dqp_al_banded_wide.hip,
+// which includes this file's templates.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -93,7 +97,7 @@ template <class Map> struct BandCfg {
     // problem.  (Lane-major rows -- [r ROW + c] -- made every instruction touch 64 separate cache lines: the factor is
     // 111 KB per quadrotor problem, written by the forward sweep and read by the backward sweep of every Newton step.)
     static constexpr int ROW = NT + 1 + NX;
-    static_assert(NT <= 16, "one knot must fit a 16-lane DPP row");
+    static_assert(NT <= 32, "one knot must fit a 32-lane half-wavefront");
 };
 
 // ---- lane groups.  A knot of nt <= 8 rows uses half of a 16-lane DPP row; the models this solver is run on
@@ -105,6 +109,12 @@ template <int G> struct Grp;
 template <> struct Grp<16> {
     __device__ __forceinline__ static double rb(double v, int k) { return dqp::r16::rb(v, k); }
     __device__ __forceinline__ static double sum(double v) { return row_sum(v); }
+};
+// Grp<32>: one problem per half-wavefront of two rows -- the row's DPP result, then one v_permlane16_swap of two copies
+// of it (bc<32> / gsum<32> of dqp_r16_prims.h, as the wide stage-wise kernels of dqp_ric.hip)
+template <> struct Grp<32> {
+    __device__ __forceinline__ static double rb(double v, int k) { return bc<32>(v, k); }
+    __device__ __forceinline__ static double sum(double v) { return gsum<32>(v); }
 };
 template <int K> __device__ __forceinline__ double rb8k(double v)
 {
@@ -268,8 +278,8 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
     double *lf = lf_dyn + (lane / G) * NT + (inT ? r : 0);          // + (t LROW + k) NL
     BAND_STAMP_INIT;
     if constexpr (!PRE) {
-        static_assert(G == 16, "the large-model sweep keeps one knot per DPP row");
-        // transposed copy of M_t (nt rows over the lanes, nx columns in registers) in the tile: columns nx .. 15 stay zero,
+        static_assert(G >= 16, "the large-model sweep keeps one knot per DPP row or half-wavefront");
+        // transposed copy of M_t (nt rows over the lanes, nx columns in registers) in the tile: columns nx .. G - 1 stay zero,
         // lanes beyond nx read them and so subtract nothing
     #pragma unroll
         for (int j = NX; j < G; ++j) trow[j * TS] = 0.0;
@@ -786,6 +796,19 @@ __global__ __launch_bounds__(64) void al_banded_solve_kernel(BandP P)
     }
 }
 
+// (n_state, n_ctrl) pairs with a caller-linearised instantiation
+#define DQP_BAND_SIZES                                                                                   \
+    X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(6, 1) X(7, 1) X(8, 1) X(2, 2) X(3, 2) X(4, 2) X(5, 2) X(6, 2) X(8, 2) \
+    X(10, 2) X(12, 2) X(3, 3) X(6, 3) X(9, 3) X(4, 4) X(6, 4) X(8, 4) X(10, 4) X(12, 4)
+
+// the wide pairs (16 < n_state + n_ctrl <= 32: Given<n, m> on Grp<32>, the large-model sweep and the solve kernel only),
+// the ones the stage-wise PDIPM kernels have (dqp_ric_wide.hip); instantiated in dqp_al_banded_wide.hip
+#define DQP_BAND_WIDE_SIZES X(13, 4) X(14, 7) X(24, 8)
+
+#ifdef DQP_AL_BANDED_KERNELS_ONLY      // dqp_al_banded_wide.hip includes the templates above and instantiates its own pairs
+}  // namespace
+#else
+
 // Eight problems per wavefront where a knot fits a half row AND the batch is more than one wavefront per SIMD at
 // four per wavefront (these kernels hold one wavefront per SIMD): below that the launch is one latency chain per
 // wavefront either way and the narrower group only idles SIMDs (cartpole-1 at B = 4096: 2.0 ms both ways;
@@ -847,15 +870,17 @@ template <class Map> int run_solve(const BandP &P, void *stream)
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
-// (n_state, n_ctrl) pairs with a caller-linearised instantiation
-#define DQP_BAND_SIZES                                                                                   \
-    X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(6, 1) X(7, 1) X(8, 1) X(2, 2) X(3, 2) X(4, 2) X(5, 2) X(6, 2) X(8, 2) \
-    X(10, 2) X(12, 2) X(3, 3) X(6, 3) X(9, 3) X(4, 4) X(6, 4) X(8, 4) X(10, 4) X(12, 4)
-
 bool given_supported(int n, int m)
 {
 #define X(a, b) if (n == a && m == b) return true;
     DQP_BAND_SIZES
+#undef X
+    return false;
+}
+bool given_wide(int n, int m)
+{
+#define X(a, b) if (n == a && m == b) return true;
+    DQP_BAND_WIDE_SIZES
 #undef X
     return false;
 }
@@ -869,6 +894,15 @@ int knot_doubles(int id, int n_, int m_)          // nt rows x (L row, 1/diag, M
 }
 
 }  // namespace
+
+namespace dqp {
+// dqp_al_banded_wide.hip: the launches of the DQP_BAND_WIDE_SIZES pairs.  `bandp` is a BandP of `bandp_bytes` bytes: the
+// struct is private to each translation unit (both compile this file's definition, and the kernels' names carry it), so
+// the callee checks the size it was compiled with and refuses another (DQP_ERR_BAD_ARG).  DQP_ERR_TOO_LARGE: no kernel
+// for (n, m).
+int al_banded_wide_newton(int n_state, int n_ctrl, const void *bandp, size_t bandp_bytes, void *stream);
+int al_banded_wide_solve(int n_state, int n_ctrl, const void *bandp, size_t bandp_bytes, void *stream);
+}  // namespace dqp
 
 using namespace dqp::dyn;
 
@@ -884,6 +918,15 @@ __attribute__((visibility("default"))) size_t dqp_al_banded_factor_bytes(const d
     const int kd = d ? knot_doubles(dyn_id, d->n_state, d->n_ctrl) : 0;
     if (!d || d->nbatch <= 0 || d->T < 2 || kd == 0) return 0;
     return (size_t)d->nbatch * d->T * kd * sizeof(double);
+}
+
+// the factor buffer of dqp_al_banded_newton_step_jac: the narrow pairs' size, or the same layout at a wide pair
+__attribute__((visibility("default"))) size_t dqp_al_banded_jac_factor_bytes(const dqp_al_mpc_dims *d)
+{
+    if (!d || d->nbatch <= 0 || d->T < 2) return 0;
+    const int n = d->n_state, nt = d->n_state + d->n_ctrl;
+    if (!given_supported(n, d->n_ctrl) && !given_wide(n, d->n_ctrl)) return 0;
+    return (size_t)d->nbatch * d->T * nt * (nt + 1 + n) * sizeof(double);
 }
 
 }  // extern "C"
@@ -939,7 +982,7 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
 #define X(a, b) if (d->n_state == a && d->n_ctrl == b) return run_solve<Given<a, b>>(P, stream);
         DQP_BAND_SIZES
 #undef X
-        return DQP_ERR_TOO_LARGE;
+        return dqp::al_banded_wide_solve(d->n_state, d->n_ctrl, &P, sizeof(P), stream);
     }
     switch (dyn_id) {
     case DQP_DYN_PENDULUM1L: return run_solve<Robot<Pendulum1l>>(P, stream);
@@ -961,7 +1004,7 @@ dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *d, const double *xu, const 
                               double *update, void *factor, int32_t *info, void *stream)
 {
     if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
-    if (!given_supported(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
+    if (!given_supported(d->n_state, d->n_ctrl) && !given_wide(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
     if (d->nbatch == 0) return DQP_OK;
     if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !x_next || !Jx || !Ju || !update || !factor)
         return DQP_ERR_BAD_ARG;
@@ -970,7 +1013,7 @@ dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *d, const double *xu, const 
 #define X(a, b) if (d->n_state == a && d->n_ctrl == b) return run_newton<Given<a, b>>(P, stream);
     DQP_BAND_SIZES
 #undef X
-    return DQP_ERR_TOO_LARGE;
+    return dqp::al_banded_wide_newton(d->n_state, d->n_ctrl, &P, sizeof(P), stream);
 }
 
 __attribute__((visibility("default"))) int dqp_al_lane_group(int width)
@@ -981,3 +1024,5 @@ __attribute__((visibility("default"))) int dqp_al_lane_group(int width)
 }
 
 }  // extern "C"
+
+#endif  // DQP_AL_BANDED_KERNELS_ONLY

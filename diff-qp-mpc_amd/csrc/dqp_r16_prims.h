@@ -56,6 +56,41 @@ __device__ __forceinline__ double row_max(double v)
     return v;
 }
 
+// ------------------------------------------------------------------ lane groups of 16 or 32
+// Cross-lane primitives over the G lanes of one problem.  G = 16: the DPP row ones.  G = 32 (two rows):
+// the row's own DPP result, then v_permlane16_swap of two copies of it, which swaps the odd rows of the
+// first with the even rows of the second -- the first then holds row 0's value of each half-wavefront,
+// the second row 1's, in all 32 lanes of the half (the compiler places the VALU-write wait states).
+__device__ __forceinline__ void half_rows(double x, double &row0, double &row1)
+{
+    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(x), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(x), false, false);
+    row0 = __hiloint2double(hi[0], lo[0]);
+    row1 = __hiloint2double(hi[1], lo[1]);
+}
+// value of lane k of the problem's lanes, in all of them (k a compile-time constant after unrolling)
+template <int G> __device__ __forceinline__ double bc(double v, int k)
+{
+    if constexpr (G == 16) return rb(v, k);
+    double a, b;
+    half_rows(rb(v, k & 15), a, b);
+    return k < 16 ? a : b;
+}
+template <int G> __device__ __forceinline__ double gsum(double v)
+{
+    if constexpr (G == 16) return row_sum(v);
+    double a, b;
+    half_rows(row_sum(v), a, b);
+    return a + b;
+}
+template <int G> __device__ __forceinline__ double gmin(double v)
+{
+    if constexpr (G == 16) return row_min(v);
+    double a, b;
+    half_rows(row_min(v), a, b);
+    return fmin(a, b);
+}
+
 // Pins a value's definition where it is written: without it the compiler may sink a per-step
 // `if (r == k) rd = x` select to the first use of rd, keeping all N candidates x alive (60 VGPRs
 // through the next phase) -- seen in the null-space backward kernel: 5.7 KB/lane of spills.

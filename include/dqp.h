@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-#define DQP_VERSION 302 /* 0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
+#define DQP_VERSION 303 /* 0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
+                           (compiled pairs), dqp_al_banded_jac_factor_bytes;
+                           0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
                            0.3.1: stage-wise MPC kernels for 16 < n_state + n_ctrl <= 32 (compiled pairs), same entry points;
                            0.3.0: DQP_FLAG_STRICT_GET_STEP, dqp_mpc_qp_forward_stepped (caller-supplied equality
                            residual, one PDIPM iteration range per call), dqp_trace_begin / dqp_trace_end, DQP_MAX_DIM_LARGE
@@ -505,10 +507,18 @@ int dqp_al_banded_solve(const dqp_al_mpc_dims *dims, int dyn_id, const void *fac
  * deqmpc/envs.py:50-82 or RexQuadrotor_dynamics_jac (rex_quadrotor.py:131-146) -- at any horizon:
  * x_next (B,T-1,n) = f(x_t,u_t), Jx (B,T-1,n,n) = df/dx, Ju (B,T-1,n,m) = df/du instead of a registered
  * model.  Lifts the nz <= 128 limit of dqp_al_newton_step for user dynamics (config 4 with the reference's
- * own quadrotor module: nz = 480).  Compiled (n_state, n_ctrl) pairs: DQP_BAND_SIZES in csrc/dqp_al_banded.hip;
- * others return DQP_ERR_TOO_LARGE.  The factor has the layout of dqp_al_banded_factor_bytes(dims, 0) and is
- * applied by dqp_al_banded_solve(dims, 0, ...).
+ * own quadrotor module: nz = 480).  Compiled (n_state, n_ctrl) pairs: DQP_BAND_SIZES (n_state + n_ctrl <= 16: one
+ * problem per 8 or 16 lanes) and DQP_BAND_WIDE_SIZES (16 < n_state + n_ctrl <= 32: one problem per 32-lane
+ * half-wavefront, csrc/dqp_al_banded_wide.hip) in csrc/dqp_al_banded.hip; others return DQP_ERR_TOO_LARGE.
+ * `factor` has dqp_al_banded_jac_factor_bytes(dims) bytes and is applied by dqp_al_banded_solve(dims, 0, ...).
+ *
+ * dqp_al_banded_jac_factor_bytes: the factor buffer size of this call at every pair it accepts -- at the
+ * DQP_BAND_SIZES pairs the value of dqp_al_banded_factor_bytes(dims, 0), at the DQP_BAND_WIDE_SIZES pairs
+ * 8 B T nt (nt + 1 + n_state) with nt = n_state + n_ctrl (the same per-knot layout); 0 for T < 2, nbatch <= 0, a null
+ * `dims` or a pair that is not compiled.  dqp_al_banded_factor_bytes(dims, 0) itself stays 0 at the wide pairs
+ * (callers read a zero there as "no 8- / 16-lane kernel").
  */
+size_t dqp_al_banded_jac_factor_bytes(const dqp_al_mpc_dims *dims);
 int dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *dims, const double *xu, const double *x0,
                                   const double *Qdiag, const double *q, const double *lam, const double *rho,
                                   const double *u_lower, const double *u_upper, const double *x_next,
@@ -517,7 +527,8 @@ int dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *dims, const double *xu,
 
 /* Testing / A-B runs: pins how many lanes a problem of the block-tridiagonal kernels occupies (8: two problems per
  * 16-lane DPP row where n_state + n_ctrl <= 8; 16: one per row; 0: chosen from the batch size and the device's CU
- * count, the default).  The environment variable DQP_AL_LANE_GROUP=8|16 sets the initial value (read once). */
+ * count, the default).  The environment variable DQP_AL_LANE_GROUP=8|16 sets the initial value (read once).  The
+ * DQP_BAND_WIDE_SIZES pairs always take a 32-lane half-wavefront and ignore it. */
 int dqp_al_lane_group(int width);
 
 /* ----------------------------------------------------------------- device dynamics registry */
