@@ -42,10 +42,11 @@ DQP_STATUS_Q_NOT_PD = 1
 DQP_STATUS_A_RANK_DEF = 2
 DQP_MAX_DIM = 64
 DQP_MAX_DIM_LARGE = 512
+SHARED_GRAD_KC = 64      # samples per split-K chunk of dqp_qp_backward_shared (csrc/dqp_shared_grad.hip: KC)
 
 # every symbol include/dqp.h declares
 SYMBOLS = ("dqp_version", "dqp_error_string", "dqp_workspace_bytes", "dqp_termination_bytes",
-           "dqp_qp_forward", "dqp_qp_backward", "dqp_term_local_masks", "dqp_qp_forward_finish", "dqp_mpc_assemble", "dqp_mpc_assemble_backward",
+           "dqp_qp_forward", "dqp_qp_backward", "dqp_qp_backward_shared_bytes", "dqp_qp_backward_shared", "dqp_term_local_masks", "dqp_qp_forward_finish", "dqp_mpc_assemble", "dqp_mpc_assemble_backward",
            "dqp_mpc_qp_supported", "dqp_mpc_qp_workspace_bytes", "dqp_mpc_qp_host_n_state", "dqp_mpc_qp_termination_bytes", "dqp_mpc_qp_forward", "dqp_mpc_qp_backward", "dqp_mpc_line_search", "dqp_mpc_rollout_backward",
            "dqp_al_newton_step", "dqp_al_chol_solve", "dqp_al_assemble", "dqp_al_merit",
            "dqp_al_newton_solve_bytes", "dqp_al_newton_solve",
@@ -116,6 +117,10 @@ def load():
     lib.dqp_qp_forward_finish.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 16
     lib.dqp_qp_backward.restype = ctypes.c_int
     lib.dqp_qp_backward.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 17
+    lib.dqp_qp_backward_shared_bytes.restype = ctypes.c_size_t
+    lib.dqp_qp_backward_shared_bytes.argtypes = [ctypes.POINTER(dqp_dims)]
+    lib.dqp_qp_backward_shared.restype = ctypes.c_int
+    lib.dqp_qp_backward_shared.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 18
     lib.dqp_mpc_assemble.restype = ctypes.c_int
     lib.dqp_mpc_assemble.argtypes = [ctypes.POINTER(dqp_mpc_dims)] + [_dp] * 14
     lib.dqp_mpc_assemble_backward.restype = ctypes.c_int

@@ -45,6 +45,10 @@ MASK_EXCHANGE = None
 # extra dqp_opts.flags OR-ed into every call (tests use DQP_FLAG_GENERIC_ONLY / _NO_NULLSPACE to
 # pin a kernel family; 0 = automatic dispatch)
 FORCE_FLAGS = 0
+# gradients of parameters without a batch dimension: True -> summed over the batch on the device
+# (dqp_qp_backward_shared: no per-sample dQ/dG/dA is ever written); False -> per-sample gradients + .mean(0),
+# the path of earlier versions (kept for A/B comparisons; same value up to the order of the summation)
+REDUCE_SHARED_GRADS = True
 
 
 # How QPFunction's result checks reach the host (`check_Q_spd` -> RuntimeError('Q is not SPD.'), qp.py:86; the INACC_ERR
@@ -194,29 +198,44 @@ def _forward_impl(Q_, p_, G_, h_, A_, b_, eps, maxIter, notImprovedLim, terminat
     return zhat, lam, nu, slack, info, resid, (Q, G, A, dims, ctx_ws)
 
 
-def _backward_impl(saved, zhat, lam, nu, slack, dl_dzhat, need, flags):
+def _backward_impl(saved, zhat, lam, nu, slack, dl_dzhat, need, flags, shared=None):
+    """-> (dQ, dp, dG, dh, dA, db).  `shared` (six bools, or None) marks the parameters whose gradient comes back as
+    ONE unbatched tensor, the SUM over the batch (dqp_qp_backward_shared); every other one is per sample."""
     lib = _lib.load()
     Q, G, A, dims, ctx_ws = saved
     nBatch, nz, nineq, neq = dims.nbatch, dims.nz, dims.nineq, dims.neq
     dev = Q.device
     kw = dict(dtype=torch.float64, device=dev)
     g = dl_dzhat.detach().double().contiguous()
-    dQ = torch.empty(nBatch, nz, nz, **kw) if need[0] else None
-    dp = torch.empty(nBatch, nz, **kw) if need[1] else None
-    dG = torch.empty(nBatch, nineq, nz, **kw) if need[2] else None
-    dh = torch.empty(nBatch, nineq, **kw) if need[3] else None
-    dA = torch.empty(nBatch, neq, nz, **kw) if (need[4] and neq > 0) else None
-    db = torch.empty(nBatch, neq, **kw) if (need[5] and neq > 0) else None
+    shared = tuple(shared) if shared is not None else (False,) * 6
+    lead = [() if sh else (nBatch,) for sh in shared]
+    dQ = torch.empty(*lead[0], nz, nz, **kw) if need[0] else None
+    dp = torch.empty(*lead[1], nz, **kw) if need[1] else None
+    dG = torch.empty(*lead[2], nineq, nz, **kw) if need[2] else None
+    dh = torch.empty(*lead[3], nineq, **kw) if need[3] else None
+    dA = torch.empty(*lead[4], neq, nz, **kw) if (need[4] and neq > 0) else None
+    db = torch.empty(*lead[5], neq, **kw) if (need[5] and neq > 0) else None
     big = max(nz, nineq, neq) > _lib.DQP_MAX_DIM
     if ctx_ws is not None and (big or not (FORCE_FLAGS & (_lib.DQP_FLAG_NO_NULLSPACE | _lib.DQP_FLAG_GENERIC_ONLY))):
         flags |= _lib.DQP_FLAG_BACKWARD_CTX
     opts = _lib.dqp_opts(0.0, 0.0, 0, 0, flags | FORCE_FLAGS, 0)
-    with torch.cuda.device(dev):
-        rc = lib.dqp_qp_backward(ctypes.byref(dims), ctypes.byref(opts), _ptr(Q), _ptr(G), _ptr(A),
-                                 _ptr(zhat), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(g),
-                                 _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
-                                 ctypes.c_void_p(0), _ptr(ctx_ws), _stream(dev))
-    _lib.check(rc, "dqp_qp_backward")
+    args = (ctypes.byref(dims), ctypes.byref(opts), _ptr(Q), _ptr(G), _ptr(A),
+            _ptr(zhat), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(g),
+            _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
+            ctypes.c_void_p(0), _ptr(ctx_ws))
+    if any(shared):
+        # `dims` carries stride 0 for exactly the parameters without a batch dimension (_prep)
+        strides = (dims.stride_Q, dims.stride_p, dims.stride_G, dims.stride_h, dims.stride_A, dims.stride_b)
+        assert all(st == 0 for st, sh in zip(strides, shared) if sh)
+        rb = int(lib.dqp_qp_backward_shared_bytes(ctypes.byref(dims)))
+        reduce_ws = torch.empty(rb // 8, **kw)
+        with torch.cuda.device(dev):
+            rc = lib.dqp_qp_backward_shared(*args, _ptr(reduce_ws), _stream(dev))
+        _lib.check(rc, "dqp_qp_backward_shared")
+    else:
+        with torch.cuda.device(dev):
+            rc = lib.dqp_qp_backward(*args, _stream(dev))
+        _lib.check(rc, "dqp_qp_backward")
     return dQ, dp, dG, dh, dA, db
 
 
@@ -280,13 +299,15 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3, maxIter=20,
             if ctx.check is not None and ctx.check in _pending:
                 _resolve(ctx.check, True)
             need = ctx.needs_input_grad[:6]
+            reduce = REDUCE_SHARED_GRADS and any(ctx.shared)
             grads = list(_backward_impl(ctx.saved, zhat, ctx.lams, ctx.nus, ctx.slacks,
-                                        dl_dzhat, need, 0))
+                                        dl_dzhat, need, 0, ctx.shared if reduce else None))
+            nBatch = ctx.saved[3].nbatch
             for i, g in enumerate(grads):
                 if g is None:
                     continue
-                if ctx.shared[i]:
-                    g = g.mean(0)                                    # qp.py:160-178
+                if ctx.shared[i]:                                    # qp.py:160-178: the mean over the batch
+                    g = g / nBatch if reduce else g.mean(0)
                 grads[i] = g.to(ctx.out_dtype)
             return tuple(grads) + (None, None)
 

@@ -112,7 +112,13 @@ def reduce_shared_grad_from_local_mean(g_local_mean, n_local, nbatch, group=None
 
 
 def reduce_shared_grad(g_local_sum, nbatch, group=None):
-    """g_local_sum: SUM over the local shard of per-sample gradients of a shared parameter."""
+    """g_local_sum: SUM over the local shard of per-sample gradients of a shared parameter -- what
+    dqp_qp_backward_shared writes for a stride-0 parameter (qp._backward_impl with a `shared` mask), e.g.
+
+        dQ, dp, dG, dh, dA, db = qp._backward_impl(saved, zhat, lam, nu, slack, dl_dzhat, need, 0,
+                                                   shared=(True, False, True, False, True, False))
+        dQ = sharding.reduce_shared_grad(dQ, nbatch, group)      # the reference's .mean(0) over the FULL batch
+    """
     g = g_local_sum.clone()
     dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
     return g / nbatch

@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-#define DQP_VERSION 303 /* 0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
+#define DQP_VERSION 303 /* (additive at 303, no bump: dqp_qp_backward_shared_bytes / dqp_qp_backward_shared -- gradients of
+                           shared parameters summed over the batch on the device;)
+                           0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
                            0.3.1: stage-wise MPC kernels for 16 < n_state + n_ctrl <= 32 (compiled pairs), same entry points;
@@ -213,7 +215,8 @@ int dqp_qp_forward(const dqp_dims *dims, const dqp_opts *opts,
  *           (qp.py:239-270).
  * Writes PER-SAMPLE gradients dQ (B,nz,nz) dp (B,nz) dG (B,nineq,nz) dh (B,nineq)
  * dA (B,neq,nz) db (B,neq); the caller applies .mean(0) for parameters that were shared
- * (qp.py:160-178).  Any gradient pointer may be NULL to skip it.
+ * (qp.py:160-178), or calls dqp_qp_backward_shared (below), which sums them on the device.
+ * Any gradient pointer may be NULL to skip it.
  */
 int dqp_qp_backward(const dqp_dims *dims, const dqp_opts *opts,
                     const double *Q, const double *G, const double *A,
@@ -221,6 +224,36 @@ int dqp_qp_backward(const dqp_dims *dims, const dqp_opts *opts,
                     const double *slack, const double *dl_dzhat,
                     double *dQ, double *dp, double *dG, double *dh, double *dA, double *db,
                     int32_t *info, void *workspace, void *stream);
+
+/*
+ * dqp_qp_backward for parameters that are SHARED by the batch (stride 0 in `dims`): the gradient pointer of every
+ * such parameter receives ONE unbatched tensor, the SUM over the batch of the per-sample gradients --
+ * dQ (nz,nz) dp (nz) dG (nineq,nz) dh (nineq) dA (neq,nz) db (neq) -- and no per-sample copy of it is ever written.
+ * The caller divides by nbatch for the reference's .mean(0) (qp.py:160-178); a sum is what an all-reduce over the
+ * shards of a larger batch consumes.  Parameters with a non-zero stride get per-sample gradients exactly as from
+ * dqp_qp_backward (the same kernel writes them); any gradient pointer may be NULL; the flags mean what they mean there.
+ *
+ * How: the per-sample kernel of the size's family runs with NULL outputs for the shared matrices and leaves
+ * dx, -dlam, -dnu (B, .) in the caller's buffers or in `reduce_ws`; the sums sum_b dG_b = DLAM^T Z + LAM^T DX etc. are
+ * split-K GEMMs over the batch on the fp64 matrix cores (64 samples per chunk, one 16 x 16 tile per wavefront, every
+ * sample's term rounded as the per-sample kernels round it, partial tiles in `reduce_ws`), finished by a kernel that
+ * adds the partials in ascending chunk order.  No atomics: the
+ * result depends only on the inputs and nbatch and is bit-identical from run to run.  Three enqueues, no
+ * synchronisation, no allocation.
+ *
+ * reduce_ws: dqp_qp_backward_shared_bytes(dims) bytes of device scratch (8-byte aligned) =
+ *   8 * (nbatch (nz + nineq + neq) + ceil(nbatch / 64) * T * 256),  T = 16 x 16 tiles of the shared parameters' gradients;
+ * 0 when no parameter is shared (the call is then dqp_qp_backward and reduce_ws may be NULL).  A host function: it
+ * needs no device.  With a shared parameter and reduce_ws == NULL: DQP_ERR_BAD_ARG.  nbatch == 0: DQP_OK, nothing
+ * is written.  nbatch <= 64 * 65535.
+ */
+size_t dqp_qp_backward_shared_bytes(const dqp_dims *dims);
+int dqp_qp_backward_shared(const dqp_dims *dims, const dqp_opts *opts,
+                           const double *Q, const double *G, const double *A,
+                           const double *zhat, const double *lam, const double *nu,
+                           const double *slack, const double *dl_dzhat,
+                           double *dQ, double *dp, double *dG, double *dh, double *dA, double *db,
+                           int32_t *info, void *workspace, void *reduce_ws, void *stream);
 
 /* ------------------------------------------------------------------ MPC-structured QPs */
 
