@@ -22,6 +22,11 @@ FUSED_NEWTON_AL = True
 # registered device models with a block-tridiagonal kernel: the whole al_solve (warm start, al_iter x [Newton steps,
 # multiplier update]) as one C-ABI call, dqp_al_mpc_solve; False: one call per Newton solve and outer update (round 2)
 ONE_CALL_SOLVE = True
+# small batches: the one-call solve as ONE kernel launch (dqp_al_mpc_solve_fused: a problem per wavefront, the problem in
+# LDS for the whole solve) where the model has it (n_state + n_ctrl <= 8, T <= 32) and B <= PERSISTENT_SOLVE_MAX_BATCH.
+# Off by default: the same arithmetic up to summation order, not the same kernels as the per-launch paths.
+PERSISTENT_SOLVE = False
+PERSISTENT_SOLVE_MAX_BATCH = 0
 # one host synchronisation per al_solve to look at the Cholesky-failure flags of the device path
 # (False: never look -- needed to capture a call in a hipGraph; a failed factorisation then leaves its
 # problem at the last accepted iterate)
@@ -143,9 +148,11 @@ class MPC(Module):
             lamda = self.lamda_prev.to(dt) if lamda_init is None else lamda_init
             rho = self.rho_prev if rho_init is None else rho_init
             prev = None if self.just_initialized else self._device_history()
+            persistent = (PERSISTENT_SOLVE and x.size(0) <= PERSISTENT_SOLVE_MAX_BATCH
+                          and al_utils.fused_solve_supported(x.size(0), dx, self.T))
             xu, hc, hl, hr, resn, fail = al_utils.ALSolveDevice.apply(          # the iterate enters detached (AL_mpc.py:287)
                 x.detach(), u.detach(), x0.detach(), cost.C.to(dt), cost.c.to(dt), lamda.detach(), rho.detach(), dx,
-                self.u_lower, self.u_upper, self.al_iter, prev)
+                self.u_lower, self.u_upper, self.al_iter, prev, persistent)
             self.fail_log.append(fail)          # per-AL-iteration Cholesky-failure flags of the calls since reinitialize()
             if CHECK_CHOLESKY and bool(fail.any()):
                 # a Cholesky factorisation broke down somewhere in the batch: the reference then switches the batch to an

@@ -536,10 +536,12 @@ class ALSolveDevice(torch.autograd.Function):
     start, al_iter x [four Newton steps with line search, multiplier / penalty update], no host involvement), and
     NewtonAL's backward through the last block-tridiagonal factor.  `prev` = (cost, lam, rho) history tensors of
     the previous call or None.  Returns xu (B,T,nt) and, non-differentiable, the new history (cost (K,B), lam
-    (K,B,ncon), rho (K,B)), |res_clamp| (B) and the per-AL-iteration Cholesky-failure flags (int32)."""
+    (K,B,ncon), rho (K,B)), |res_clamp| (B) and the per-AL-iteration Cholesky-failure flags (int32).
+    `fused`: the single-launch entry dqp_al_mpc_solve_fused (small batches; fused_solve_supported says where it
+    exists) instead of the launch train -- the same arguments, outputs and backward."""
 
     @staticmethod
-    def forward(ctx, x_init, u_init, x0, Q, q, lam, rho, dyn, u_lower, u_upper, al_iter, prev):
+    def forward(ctx, x_init, u_init, x0, Q, q, lam, rho, dyn, u_lower, u_upper, al_iter, prev, fused=False):
         lib = _lib.load()
         B, T, n = x_init.shape
         m = u_init.shape[-1]
@@ -559,11 +561,12 @@ class ALSolveDevice(torch.autograd.Function):
         L = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), dyn.id)) // 8, **kw)
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8 + 1, **kw)
+        entry, name = (lib.dqp_al_mpc_solve_fused, "dqp_al_mpc_solve_fused") if fused else (lib.dqp_al_mpc_solve, "dqp_al_mpc_solve")
         with torch.cuda.device(dev):
-            rc = lib.dqp_al_mpc_solve(ctypes.byref(dims), dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *[_ptr(t) for t in keep],
-                                      _ptr(pc), _ptr(pl), _ptr(pr), n_prev, _ptr(xu), _ptr(hc), _ptr(hl), _ptr(hr), _ptr(resn),
-                                      _ptr(L), _ptr(status), _ptr(fail), _ptr(ws), _stream(dev))
-        _lib.check(rc, "dqp_al_mpc_solve")
+            rc = entry(ctypes.byref(dims), dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *[_ptr(t) for t in keep],
+                       _ptr(pc), _ptr(pl), _ptr(pr), n_prev, _ptr(xu), _ptr(hc), _ptr(hl), _ptr(hr), _ptr(resn),
+                       _ptr(L), _ptr(status), _ptr(fail), _ptr(ws), _stream(dev))
+        _lib.check(rc, name)
         ctx.dims, ctx.dyn_id = dims, dyn.id
         ctx.save_for_backward(L, xu)
         ctx.mark_non_differentiable(hc, hl, hr, resn, fail)
@@ -577,7 +580,13 @@ class ALSolveDevice(torch.autograd.Function):
         with torch.cuda.device(rhs.device):
             rc = _lib.load().dqp_al_banded_solve(ctypes.byref(ctx.dims), ctx.dyn_id, _ptr(L), _ptr(rhs), _ptr(g), _stream(rhs.device))
         _lib.check(rc, "dqp_al_banded_solve")
-        return (None,) * 3 + (g * x, g) + (None,) * 7                      # al_utils.py:482-485
+        return (None,) * 3 + (g * x, g) + (None,) * 8                      # al_utils.py:482-485
+
+
+def fused_solve_supported(n_batch, dyn, T):
+    """dqp_al_mpc_solve_fused exists for this registered model and horizon (n_state + n_ctrl <= 8, 2 <= T <= 32)"""
+    dims = _lib.dqp_al_mpc_dims(n_batch, dyn.n_state, dyn.n_ctrl, T)
+    return bool(_lib.load().dqp_al_mpc_solve_fused_supported(ctypes.byref(dims), dyn.id))
 
 
 def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper):

@@ -1,0 +1,486 @@
+// dqp_al_fused.hip -- AL_mpc.MPC.al_solve for a registered device model as ONE kernel launch (dqp_al_mpc_solve_fused).
+//
+// dqp_al_mpc_solve (dqp_al.hip) is a train of 25 to 30 launches at al_iter = 2: al_start_kernel, then per AL iteration
+// a merit launch, four x [al_banded_newton_kernel, al_ls_group_kernel (+ al_select_kernel)] and al_outer_kernel.  At
+// the reference's training batch (B = 128) every one of them is a 20 - 30 us latency chain on a handful of wavefronts
+// that re-reads xu, Qd, q and lam from HBM.  Everything in al_solve is independent per problem (the sticky
+// cholesky_fail switch aside, which stays a flag the host looks at), so here one problem is one workgroup of ONE
+// wavefront that runs the whole solve with the problem on chip:
+//
+//   LDS       xu, upd, y, Qd, q (T nt each), lam (ncon), the Jacobian columns / residuals of every knot, the
+//             block-tridiagonal factor of the current Newton step, the 20 candidate merits
+//   model     the wavefront is eight 8-lane groups (Grp<8>, a knot of nt <= 8 rows per group).  The forward-mode
+//             Jacobians of a Newton step are evaluated for EIGHT knots at once: group g takes knots g, g + 8, ...,
+//             lane r of it the seed e_r -- ceil((T - 1) / 8) model evaluations per step on the chain instead of T - 1
+//   sweep     the block Cholesky sweep of al_banded_newton_kernel (the same primitives: chol_g, unit_lower, trsv_unit,
+//             trsvT_bcast), replicated in the eight groups -- a SIMD instruction costs the same for 8 or 64 lanes, and
+//             no group waits for another; group 0 writes the factor and the update to LDS
+//   search    the 20 candidates xu + 2^-k upd over the groups (group g: k = g, g + 8, g + 16: three rounds instead of
+//             twenty), lane r of a group the knots r, r + 8, ...; then the wavefront argmin of al_select_kernel
+//   outer     one knot per lane: lam <- clamp(lam + rho res), cost, |res_clamp|, rho <- 10 rho, history row i + 1
+//
+// HBM sees the inputs once, then the history rows, xu, res_norm, status, fail and the ONE kept factor (the last Newton
+// step of the last AL iteration), in the layout dqp_al_banded_solve reads: per (b, t) element c of lane r's row at
+// [c nt + r] -- the same for every lane-group width (BandCfg), so NewtonAL.backward is unchanged.
+//
+// No wait on another workgroup anywhere: no cooperative launch, no grid barrier, no flag to spin on; the barriers
+// below are workgroup barriers of a one-wavefront workgroup.  All stores are plain vector stores, the `fail` flag an
+// ordinary atomicOr as in al_select_kernel.
+//
+// Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2),
+// 2 <= T <= 32, fp64.  RexQuadrotor (12 + 4) stays on the multi-launch path.
+#define DQP_AL_BANDED_KERNELS_ONLY
+#include "dqp_al_banded.hip"
+
+namespace {
+
+struct FusedP {
+    const double *x_init, *u_init, *x0, *Qd, *q, *ul, *uu, *lam_in, *rho_in;
+    const double *prev_cost, *prev_lam, *prev_rho;      // previous call's history, oldest first, or NULL (n_prev = 0)
+    double *xu, *hist_cost, *hist_lam, *hist_rho, *res_norm, *fac, *status;
+    int32_t *fail;
+    double dt;
+    int B, T, al_iter, newton_steps, n_prev;
+};
+
+constexpr int FG = 8, FNG = 64 / FG;      // lanes per group, groups per wavefront
+constexpr int NCAND = 20;                 // line-search candidates 2^-k, k = 0 .. 19 (al_utils.py:503-527)
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// LDS carve of one problem, in doubles
+template <class Map> struct FusedLds {
+    using C = BandCfg<Map>;
+    static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
+    static constexpr int JBK = NX * (NT + 1);         // per knot: NX rows of [J[j][0 .. nt-1], res_j]
+    __host__ __device__ static int ncon(int T) { return T * NX + 2 * T * NU; }
+    __host__ __device__ static size_t doubles(int T)
+    {
+        return (size_t)5 * T * NT + ncon(T) + (size_t)T * JBK + (size_t)T * NT * C::ROW + 32;
+    }
+};
+
+template <class Map>
+__global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
+{
+    using C = BandCfg<Map>;
+    using Gr = Grp<FG>;
+    using Lds = FusedLds<Map>;
+    constexpr int NX = C::NX, NU = C::NU, NT = C::NT, ROW = C::ROW, JBK = Lds::JBK;
+    static_assert(NT <= FG, "a knot must fit an 8-lane group");
+    const int lane = threadIdx.x, r = lane & (FG - 1), grp = lane / FG;
+    const long long b = blockIdx.x;
+    const int T = P.T, nz = T * NT, neq = T * NX, ncon = neq + 2 * T * NU;
+    const bool inT = r < NT;
+    const int rr = inT ? r : 0, rx = r < NX ? r : 0, iu = (inT && r >= NX) ? r - NX : 0;
+
+    extern __shared__ __attribute__((aligned(16))) double fs[];
+    double *s_xu = fs, *s_upd = s_xu + nz, *s_y = s_upd + nz, *s_Qd = s_y + nz, *s_q = s_Qd + nz;
+    double *s_lam = s_q + nz, *s_jb = s_lam + ncon, *s_fac = s_jb + T * JBK, *s_merit = s_fac + T * NT * ROW;
+    // the group's tile for the transposed copies of the sweep (element (row, col) at [col TS + row])
+    constexpr int TS = FG + 2, PS = FG * TS;
+    __shared__ __attribute__((aligned(16))) double trs[FNG * PS];
+    double *trow = trs + grp * PS + r;
+    const double *tcol = trs + grp * PS + r * TS;
+
+    double x0v[NX], uuv[NU], ulv[NU];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x0v[j] = P.x0[b * NX + j];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) { uuv[i] = P.uu[i]; ulv[i] = P.ul[i]; }
+    const double x0r = P.x0[b * NX + rx], uur = P.uu[iu], ulr = P.ul[iu];
+
+    // ---- start (al_start_kernel): xu = [x_init | u_init], cost_start, warm start of (lam, rho), history row 0
+    double rho;
+    {
+        const double *Qd = P.Qd + b * (long long)nz, *q = P.q + b * (long long)nz;
+        double quad = 0.0, lin = 0.0;
+        for (int e = lane; e < nz; e += 64) {
+            const int t = e / NT, j = e - t * NT;
+            const double v = j < NX ? P.x_init[(b * T + t) * NX + j] : P.u_init[(b * T + t) * NU + (j - NX)];
+            const double qd = Qd[e], ql = q[e];
+            s_xu[e] = v; s_Qd[e] = qd; s_q[e] = ql;
+            quad += v * qd * v;
+            lin += ql * v;
+        }
+        const double cost0 = 0.5 * wave_sum(quad) + wave_sum(lin);       // al_utils.compute_cost, diagonal cost
+        const double *lam = P.lam_in + b * (long long)ncon;
+        double scale = 1.0;
+        rho = P.rho_in[b];
+        if (P.n_prev > 0) {
+            int pick = P.n_prev - 1;                     // torch.max of an all-False column: index 0 = the newest
+            for (int k = P.n_prev - 1; k >= 0; --k)
+                if (P.prev_cost[(long long)k * P.B + b] < cost0) { pick = k; break; }
+            const double *lh = P.prev_lam + ((long long)pick * P.B + b) * ncon;
+            double nh = 0.0, nl = 0.0;
+            for (int e = lane; e < ncon; e += 64) { nh += lh[e] * lh[e]; nl += lam[e] * lam[e]; }
+            scale = sqrt(wave_sum(nh)) / sqrt(wave_sum(nl));
+            rho = P.prev_rho[(long long)pick * P.B + b];
+        }
+        double *l0 = P.hist_lam + b * (long long)ncon;
+        for (int e = lane; e < ncon; e += 64) {
+            const double v = P.n_prev > 0 ? lam[e] * scale : lam[e];
+            s_lam[e] = v; l0[e] = v;
+        }
+        if (lane == 0) { P.hist_cost[b] = cost0; P.hist_rho[b] = rho; }
+    }
+#pragma unroll
+    for (int j = NX; j < FG; ++j) trow[j * TS] = 0.0;       // columns nx .. 7 of the M^T tile stay zero
+    __syncthreads();
+
+    // merit (al_utils.py:37-59) of xu + step upd with x_0 pinned to x0 (al_utils.py:515), terms as al_ls_group_kernel:
+    // lane r of a group sums the cost, box and dynamics terms of the knots r, r + 8, ...; in every lane of the group
+    auto merit_at = [&](double step, bool with_upd) -> double {
+        double acc = 0.0;
+        for (int t = r; t < T; t += FG) {
+            double z[NT], xn[NX];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const double u = with_upd ? s_upd[t * NT + j] : 0.0;
+                z[j] = fma(step, u, s_xu[t * NT + j]);
+                if (j < NX && t == 0) z[j] = x0v[j < NX ? j : 0];
+                acc += (0.5 * s_Qd[t * NT + j] * z[j] + s_q[t * NT + j]) * z[j];
+            }
+#pragma unroll
+            for (int i = 0; i < NU; ++i) {
+                const int row = neq + t * 2 * NU + i;
+                const double vh = z[NX + i] - uuv[i], vl = ulv[i] - z[NX + i];
+                acc += s_lam[row] * vh + s_lam[row + NU] * vl +
+                       0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
+            }
+            if (t < T - 1) {
+                Map::template step<double>(z, z + NX, P.dt, xn);
+#pragma unroll
+                for (int j = 0; j < NX; ++j) {
+                    const double u = with_upd ? s_upd[(t + 1) * NT + j] : 0.0;
+                    const double res = fma(step, u, s_xu[(t + 1) * NT + j]) - xn[j];
+                    acc += (0.5 * rho * res + s_lam[t * NX + j]) * res;
+                }
+            }
+        }
+        return Gr::sum(acc);
+    };
+
+    double take_last = 0.0;
+    for (int it = 0; it < P.al_iter; ++it) {
+        double merit_cur = merit_at(0.0, false);           // merit at the start of this AL iteration
+        int bad_any = 0;
+        for (int ns = 0; ns < P.newton_steps; ++ns) {
+            // ---- Jacobian column r of knots grp, grp + 8, ...: one forward-mode seed per lane
+            for (int t = grp; t < T - 1; t += FNG) {
+                Dual<1> xs[NX], us[NU], out[NX];
+#pragma unroll
+                for (int j = 0; j < NX; ++j) { xs[j] = Dual<1>(s_xu[t * NT + j]); xs[j].d[0] = (r == j) ? 1.0 : 0.0; }
+#pragma unroll
+                for (int j = 0; j < NU; ++j) { us[j] = Dual<1>(s_xu[t * NT + NX + j]); us[j].d[0] = (r == NX + j) ? 1.0 : 0.0; }
+                Map::template step<Dual<1>>(xs, us, P.dt, out);
+#pragma unroll
+                for (int j = 0; j < NX; ++j) {
+                    if (inT) s_jb[t * JBK + j * (NT + 1) + r] = out[j].d[0];
+                    if (r == 0) s_jb[t * JBK + j * (NT + 1) + NT] = s_xu[(t + 1) * NT + j] - out[j].v;   // x_{t+1} - f(x_t, u_t)
+                }
+            }
+            __syncthreads();
+            // ---- forward sweep over the knots (al_banded_newton_kernel), the same in every group
+            double Mprev[NX], yprev = 0.0, mu_prev[NX];
+            int bad = 0;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) { Mprev[j] = 0.0; mu_prev[j] = 0.0; }
+            const double lam_first = s_lam[(T - 1) * NX + rx];
+            for (int t = 0; t < T; ++t) {
+                const bool dynrow = t < T - 1;
+                const int tj = dynrow ? t : 0;
+                double Jc[NX], mu[NX];
+#pragma unroll
+                for (int j = 0; j < NX; ++j) {
+                    const double col = s_jb[tj * JBK + j * (NT + 1) + rr], res = s_jb[tj * JBK + j * (NT + 1) + NT];
+                    Jc[j] = (dynrow && inT) ? col : 0.0;
+                    mu[j] = dynrow ? s_lam[tj * NX + j] + rho * res : 0.0;
+                }
+                const double zr = s_xu[t * NT + rr], qdr = s_Qd[t * NT + rr], qr = s_q[t * NT + rr];
+                const int row = neq + t * 2 * NU + iu;
+                const double lup = s_lam[row], llo = s_lam[row + NU];
+                // gradient element r of this knot, and the diagonal terms of H_tt
+                double g = qdr * zr + qr, dg = qdr;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) g -= Jc[j] * mu[j];
+                {
+                    double prev = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) prev = (r == j) ? mu_prev[j] : prev;
+                    const double first = lam_first + rho * (zr - x0r);
+                    const double rup = zr - uur, rlo = ulr - zr;
+                    if (r < NX) {
+                        g += (t > 0) ? prev : first;
+                        dg += rho;
+                    } else if (inT) {
+                        g += (lup + rho * fmax(rup, 0.0)) - (llo + rho * fmax(rlo, 0.0));
+                        dg += rho * ((rup > 0.0 ? 1.0 : 0.0) + (rlo > 0.0 ? 1.0 : 0.0));
+                    }
+                }
+                // H_tt row r: rho J^T J + diag - Gram(M_prev) on the x-x block
+                double H[1][NT], rd[1];
+#pragma unroll
+                for (int c = 0; c < NT; ++c) {
+                    double a = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) a = fma(Jc[j], Gr::rb(Jc[j], c), a);
+                    H[0][c] = rho * a + ((r == c) ? dg : 0.0);
+                }
+                double Mt[FG];
+#pragma unroll
+                for (int k = 0; k < FG; ++k) Mt[k] = tcol[k];
+                if (t > 0) {
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        double a = 0.0;
+#pragma unroll
+                        for (int k = 0; k < NT; ++k) a = fma(Mt[k], Gr::rb(Mprev[j], k), a);
+                        H[0][j] -= a;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NT; ++c) H[0][c] = inT ? H[0][c] : ((r == c) ? 1.0 : 0.0);
+                if (!chol_g<FG, NT>(H, rd, r) && bad == 0) bad = t + 1;
+                // right-hand side: y_t = L_tt^-1 (-g_t - L_{t,t-1} y_{t-1})
+                double y = inT ? -g : 0.0;
+                if (t > 0) {
+                    double a = 0.0;
+#pragma unroll
+                    for (int k = 0; k < NT; ++k) a = fma(Mt[k], Gr::rb(yprev, k), a);
+                    y -= a;
+                }
+                double *o = s_fac + t * NT * ROW + rr;
+                const bool wr = grp == 0 && inT;
+                if (wr) {
+#pragma unroll
+                    for (int c = 0; c < NT; ++c) o[c * NT] = H[0][c];
+                    o[NT * NT] = rd[0];
+                }
+                unit_lower<FG, NT>(H, rd, r);
+                const double rdm = inT ? rd[0] : 0.0, nrho_rd = -rho * rdm;
+                y = trsv_unit<FG, NT>(H, y) * rdm;
+                // M_t = L_tt^-1 H_{t+1,t}^T: column j of it is the distributed vector -rho J[j][:]
+                double M[NX];
+#pragma unroll
+                for (int j = 0; j < NX; ++j) M[j] = trsv_unit<FG, NT>(H, Jc[j]) * nrho_rd;
+                if (wr) {
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) o[(NT + 1 + j) * NT] = M[j];
+                    s_y[t * NT + r] = y;
+                }
+#pragma unroll
+                for (int j = 0; j < NX; ++j) { Mprev[j] = M[j]; mu_prev[j] = mu[j]; }
+                yprev = inT ? y : 0.0;
+                __syncthreads();            // every lane has read M_{t-1}^T before M_t^T replaces it
+#pragma unroll
+                for (int j = 0; j < NX; ++j) trow[j * TS] = M[j];
+                __syncthreads();
+            }
+            bad_any |= bad;
+            // ---- backward sweep: upd_t = L_tt^-T (y_t - M_t upd_{t+1}[:NX])
+            double xnext = 0.0;
+            for (int t = T - 1; t >= 0; --t) {
+                const double *o = s_fac + t * NT * ROW + rr;
+                double L[1][NT], M[NX];
+#pragma unroll
+                for (int c = 0; c < NT; ++c) L[0][c] = inT ? o[c * NT] : 0.0;
+                const double rdv = inT ? o[NT * NT] : 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) M[j] = inT ? o[(NT + 1 + j) * NT] : 0.0;
+                double v = inT ? s_y[t * NT + rr] : 0.0;
+                if (t < T - 1) {
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) v = fma(-M[j], Gr::rb(xnext, j), v);
+                }
+                __syncthreads();
+                v = trsvT_bcast<FG, NT, TS>(L, rdv, v, trow, tcol, r);
+                if (grp == 0 && inT) s_upd[t * NT + r] = v;
+                xnext = inT ? v : 0.0;
+            }
+            __syncthreads();
+            // the backward sweep used the tile's columns nx .. 7: zero again for the next forward sweep
+#pragma unroll
+            for (int j = NX; j < FG; ++j) trow[j * TS] = 0.0;
+            // ---- the kept factor: the last Newton step of the last AL iteration, in dqp_al_banded_solve's layout
+            if (it == P.al_iter - 1 && ns == P.newton_steps - 1) {
+                double *fo = P.fac + b * (long long)T * NT * ROW;
+                for (int e = lane; e < T * NT * ROW; e += 64) fo[e] = s_fac[e];
+            }
+            // ---- line search: candidate k on group k % 8 (the surplus candidates of the last round are discarded)
+            for (int k0 = 0; k0 < NCAND; k0 += FNG) {
+                const int k = k0 + grp;
+                const double acc = merit_at((double)exp2f(-(float)k), true);       // float steps, as the reference
+                if (r == 0 && k < NCAND) s_merit[k] = acc;
+            }
+            __syncthreads();
+            // torch.min over the candidates (NaN wins, else the first minimum), acceptance, update of the iterate
+            {
+                const bool has = lane < NCAND;
+                const double v = has ? s_merit[lane] : INFINITY;
+                const unsigned long long nanmask = __builtin_amdgcn_ballot_w64(has && v != v);
+                double mn = (v != v) ? INFINITY : v;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_xor(mn, off, 64));
+                const unsigned long long eq = __builtin_amdgcn_ballot_w64(has && v == mn);
+                const int arg = nanmask ? (int)__builtin_ctzll(nanmask) : (eq ? (int)__builtin_ctzll(eq) : 0);
+                const double best = __shfl(v, arg, 64);
+                const bool take = best < merit_cur;
+                merit_cur = best;                                   // new_merit regardless of acceptance
+                take_last = take ? 1.0 : 0.0;
+                if (take) {
+                    const double sb = (double)exp2f(-(float)arg);
+                    for (int e = lane; e < nz; e += 64) s_xu[e] = e < NX ? P.x0[b * NX + e] : fma(sb, s_upd[e], s_xu[e]);
+                }
+            }
+            __syncthreads();
+        }
+        if (lane == 0 && bad_any != 0) atomicOr(P.fail + it, 1);    // Cholesky failed: the caller re-runs the slow path
+        // ---- outer update (al_outer_kernel): one knot per lane
+        {
+            double *ln = P.hist_lam + ((long long)(it + 1) * P.B + b) * ncon;
+            double cost = 0.0, rn2 = 0.0;
+            const int t = lane;
+            if (t < T) {
+                double z[NT], xn[NX];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) z[j] = s_xu[t * NT + j];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) cost += (0.5 * s_Qd[t * NT + j] * z[j] + s_q[t * NT + j]) * z[j];
+                if (t < T - 1) {
+                    Map::template step<double>(z, z + NX, P.dt, xn);
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        const double res = s_xu[(t + 1) * NT + j] - xn[j];
+                        rn2 += res * res;
+                        const double v = s_lam[t * NX + j] + rho * res;
+                        s_lam[t * NX + j] = v; ln[t * NX + j] = v;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        const double res = s_xu[j] - x0v[j];
+                        rn2 += res * res;
+                        const double v = s_lam[(T - 1) * NX + j] + rho * res;
+                        s_lam[(T - 1) * NX + j] = v; ln[(T - 1) * NX + j] = v;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < NU; ++i) {
+                    const double u = z[NX + i], hi = u - uuv[i], lo = ulv[i] - u;
+                    const int row = neq + t * 2 * NU + i;
+                    rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
+                    const double vu = fmax(s_lam[row] + rho * hi, 0.0), vl = fmax(s_lam[row + NU] + rho * lo, 0.0);   // AL_mpc.py:300-301
+                    s_lam[row] = vu; ln[row] = vu;
+                    s_lam[row + NU] = vl; ln[row + NU] = vl;
+                }
+            }
+            cost = wave_sum(cost);
+            rn2 = wave_sum(rn2);
+            if (lane == 0) {
+                P.hist_cost[(long long)(it + 1) * P.B + b] = cost;
+                P.res_norm[b] = sqrt(rn2);
+                P.hist_rho[(long long)(it + 1) * P.B + b] = rho * 10.0;
+            }
+            rho = rho * 10.0;                                        // AL_mpc.py:307
+        }
+        __syncthreads();
+    }
+    double *xo = P.xu + b * (long long)nz;
+    for (int e = lane; e < nz; e += 64) xo[e] = s_xu[e];
+    if (lane == 0 && P.status) P.status[b] = take_last;
+}
+
+// static LDS of the kernel (the groups' tiles) next to the dynamic carve: within the 64 KB a launch gets without opt-in
+constexpr size_t FUSED_STATIC_LDS = (size_t)FNG * FG * (FG + 2) * sizeof(double);
+constexpr size_t FUSED_LDS_LIMIT = 64 * 1024;
+
+template <class Map> size_t fused_lds_bytes(int T) { return FusedLds<Map>::doubles(T) * sizeof(double); }
+
+size_t fused_lds(int dyn_id, int T)
+{
+    using namespace dqp::dyn;
+    switch (dyn_id) {
+    case DQP_DYN_PENDULUM1L: return fused_lds_bytes<Robot<Pendulum1l>>(T);
+    case DQP_DYN_CARTPOLE1L: return fused_lds_bytes<Robot<Cartpole1l>>(T);
+    case DQP_DYN_CARTPOLE2L: return fused_lds_bytes<Robot<Cartpole2l>>(T);
+    case DQP_DYN_PENDULUM_EULER: return fused_lds_bytes<PendulumEuler>(T);
+    case DQP_DYN_PENDULUM_DX: return fused_lds_bytes<PendulumDx>(T);
+    default: return 0;
+    }
+}
+
+bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id)
+{
+    if (!d || d->T < 2 || d->T > 32 || d->nbatch < 0) return false;
+    int32_t n = 0, m = 0;
+    if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl || n + m > FG) return false;
+    const size_t lds = fused_lds(dyn_id, d->T);
+    return lds > 0 && lds + FUSED_STATIC_LDS <= FUSED_LDS_LIMIT;
+}
+
+template <class Map> int launch_fused(const FusedP &P, size_t lds, hipStream_t st)
+{
+    DQP_LAUNCH(al_solve_fused_kernel<Map>, dim3((unsigned)P.B), dim3(64), lds, st, P);
+    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default"))) int dqp_al_mpc_solve_fused_supported(const dqp_al_mpc_dims *d, int dyn_id)
+{
+    return fused_ok(d, dyn_id) ? 1 : 0;
+}
+
+// the problem lives in LDS: no workspace of its own.  The size of dqp_al_mpc_solve's is reported so that a caller that
+// switches between the two entries by name can keep one buffer.
+__attribute__((visibility("default"))) size_t dqp_al_mpc_solve_fused_bytes(const dqp_al_mpc_dims *d)
+{
+    return dqp_al_mpc_solve_bytes(d);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                       const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
+                       const double *u_lower, const double *u_upper, const double *lam_in, const double *rho_in,
+                       const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                       double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
+                       double *status, int32_t *fail, void *workspace, void *stream)
+{
+    using namespace dqp::dyn;
+    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
+        n_prev < 0)
+        return DQP_ERR_BAD_ARG;
+    if (d->nbatch == 0) return DQP_OK;
+    if (!x_init || !u_init || !x0 || !Qdiag || !q || !u_lower || !u_upper || !lam_in || !rho_in || !xu || !hist_cost ||
+        !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
+        return DQP_ERR_BAD_ARG;
+    if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
+    int32_t dn = 0, dm = 0;
+    if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (!fused_ok(d, dyn_id)) return DQP_ERR_TOO_LARGE;
+    hipStream_t st = (hipStream_t)stream;
+    // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
+    if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, st) != hipSuccess) return DQP_ERR_LAUNCH;
+    const FusedP P = {x_init, u_init, x0, Qdiag, q, u_lower, u_upper, lam_in, rho_in, prev_cost, prev_lam, prev_rho,
+                      xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, dt, d->nbatch, d->T, al_iter,
+                      newton_steps, n_prev};
+    const size_t lds = fused_lds(dyn_id, d->T);
+    switch (dyn_id) {
+    case DQP_DYN_PENDULUM1L: return launch_fused<Robot<Pendulum1l>>(P, lds, st);
+    case DQP_DYN_CARTPOLE1L: return launch_fused<Robot<Cartpole1l>>(P, lds, st);
+    case DQP_DYN_CARTPOLE2L: return launch_fused<Robot<Cartpole2l>>(P, lds, st);
+    case DQP_DYN_PENDULUM_EULER: return launch_fused<PendulumEuler>(P, lds, st);
+    case DQP_DYN_PENDULUM_DX: return launch_fused<PendulumDx>(P, lds, st);
+    default: return DQP_ERR_TOO_LARGE;
+    }
+}
+
+}  // extern "C"

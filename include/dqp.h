@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 #define DQP_VERSION 303 /* (additive at 303, no bump: dqp_qp_backward_shared_bytes / dqp_qp_backward_shared -- gradients of
-                           shared parameters summed over the batch on the device;)
+                           shared parameters summed over the batch on the device; dqp_al_mpc_solve_fused_supported /
+                           dqp_al_mpc_solve_fused_bytes / dqp_al_mpc_solve_fused -- dqp_al_mpc_solve as one launch;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -517,6 +518,33 @@ int dqp_al_mpc_solve(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t
                      const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
                      double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
                      double *status, int32_t *fail, void *workspace, void *stream);
+
+/*
+ * dqp_al_mpc_solve as ONE kernel launch, for small batches (csrc/dqp_al_fused.hip): the same arguments, outputs and
+ * arithmetic (up to summation order), so a caller switches by name.  One problem per one-wavefront workgroup; the
+ * iterate, the cost, the multipliers, the update and the factor of the current Newton step stay in LDS for the whole
+ * solve, the forward-mode Jacobians of eight knots are evaluated at once and the 20 line-search candidates are split
+ * over the wavefront's eight lane groups.  No workgroup waits for another one (no cooperative launch, no grid barrier).
+ * `factor` receives the factor of the last Newton step of the last AL iteration in the layout dqp_al_banded_solve
+ * reads (it does not depend on dqp_al_lane_group).  `fail` is cleared by a memset enqueued in front of the launch.
+ * Only enqueues on `stream` (capturable): no synchronisation, no allocation.
+ *
+ * dqp_al_mpc_solve_fused_supported: 1 for a registered model with n_state + n_ctrl <= 8 (DQP_DYN_PENDULUM1L,
+ * CARTPOLE1L, CARTPOLE2L, PENDULUM_EULER, PENDULUM_DX) at 2 <= T <= 32, else 0 (DQP_DYN_REXQUADROTOR, longer horizons:
+ * dqp_al_mpc_solve serves them).  Needs no device.  dqp_al_mpc_solve_fused returns DQP_ERR_BAD_ARG / DQP_ERR_TOO_LARGE
+ * by the rules of dqp_al_mpc_solve, DQP_ERR_TOO_LARGE wherever _supported is 0 at valid arguments, and DQP_OK at
+ * nbatch == 0 (nothing is touched).  dqp_al_mpc_solve_fused_bytes: the workspace size a caller passes -- that of
+ * dqp_al_mpc_solve_bytes, so that one buffer serves both entries; the fused kernel itself does not write to it.
+ */
+int dqp_al_mpc_solve_fused_supported(const dqp_al_mpc_dims *dims, int dyn_id);
+size_t dqp_al_mpc_solve_fused_bytes(const dqp_al_mpc_dims *dims);
+int dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                           const double *x_init, const double *u_init, const double *x0, const double *Qdiag,
+                           const double *q, const double *u_lower, const double *u_upper, const double *lam_in,
+                           const double *rho_in, const double *prev_cost, const double *prev_lam, const double *prev_rho,
+                           int32_t n_prev, double *xu, double *hist_cost, double *hist_lam, double *hist_rho,
+                           double *res_norm, double *factor, double *status, int32_t *fail, void *workspace,
+                           void *stream);
 
 /*
  * The same Newton step with the MPC structure exploited (`banded` != 0 above uses it): the Hessian

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""AL_mpc.MPC forward + backward with the single-launch solve (AL_mpc.PERSISTENT_SOLVE, dqp_al_mpc_solve_fused) off
+and on, in the same process, eager and under hipGraph replay (AL_mpc.GraphedMPC), on registered device models.
+
+The switch-off rows are the multi-launch path (dqp_al_mpc_solve) and the comparator.  Per shape and mode the two
+variants alternate in blocks of `--block` calls; a block is timed with a host clock around work that ends in a device
+synchronise, the figure is the median over the blocks, with the quartiles as the spread.  A library trace of one
+forward per variant gives the launch count and the per-kernel device time.
+
+    python tools/bench_al_fused.py [--reps 30] [--block 20] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from diff_qp_mpc_amd import AL_mpc, al_utils, _lib
+from diff_qp_mpc_amd.dynamics import DeviceDynamics
+
+SHAPES = [("pendulum_euler", 5, 128), ("cartpole1l", 20, 128), ("cartpole2l", 5, 128),
+          ("cartpole2l", 5, 32), ("cartpole2l", 5, 512), ("cartpole2l", 5, 2048), ("cartpole2l", 5, 8192)]
+
+
+def dev(a):
+    return torch.tensor(np.asarray(a), dtype=torch.float64, device="cuda")
+
+
+def setup(robot, T, B):
+    dyn = DeviceDynamics(robot)
+    nx, nu = dyn.n_state, dyn.n_ctrl
+    lim = 2.0 if robot == "pendulum_euler" else 250.0
+    lo, hi = dev(np.full(nu, -lim)), dev(np.full(nu, lim))
+    r = np.random.default_rng(0)
+    x0 = dev(r.uniform(-0.5, 0.5, (B, nx)))
+    Qd = dev(np.concatenate([np.ones(nx), 1e-3 * np.ones(nu)])).repeat(B, T, 1)
+    x_ref = x0[:, None, :] * torch.linspace(1.0, 0.0, T, dtype=torch.float64, device="cuda")[None, :, None]
+    u_ref = torch.zeros(B, T, nu, dtype=torch.float64, device="cuda")
+    C = torch.diag_embed(Qd).requires_grad_()
+    c = (-(Qd * torch.cat([x_ref, u_ref], -1))).clone().requires_grad_()
+
+    def make():
+        ctrl = AL_mpc.MPC(nx, nu, T, u_lower=lo, u_upper=hi, n_batch=B, verbose=0, solver_type="dense", dtype=torch.float64,
+                          eps=1e-5, exit_unconverged=False, backprop=False)
+        ctrl.mask = torch.ones(B, T, 1, device="cuda")
+        return ctrl
+    return dyn, make, x0, x_ref, u_ref, C, c
+
+
+def set_switch(on):
+    AL_mpc.PERSISTENT_SOLVE = on
+    AL_mpc.PERSISTENT_SOLVE_MAX_BATCH = 1 << 30
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30, help="timed blocks per variant")
+    ap.add_argument("--block", type=int, default=20, help="calls per timed block")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    try:
+        clocks = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
+    except Exception as e:      # noqa: BLE001
+        clocks = "rocm-smi --showclocks: %r" % (e,)
+    result = {"device": torch.cuda.get_device_name(0), "clocks": clocks, "reps": args.reps, "block": args.block, "rows": []}
+    for robot, T, B in SHAPES:
+        dyn, make, x0, x_ref, u_ref, C, c = setup(robot, T, B)
+        ctrl = make()
+
+        def eager():
+            ctrl.reinitialize(x0, ctrl.mask)
+            ctrl.x_init, ctrl.u_init = x_ref, u_ref
+            x, u = ctrl(x0, al_utils.QuadCost(C, c), dyn, dyn.jac)
+            torch.autograd.grad(x.double().sum() + 2.0 * u.double().sum(), (C, c))
+
+        graphs = {}
+        for on in (False, True):
+            set_switch(on)
+            graphs[on] = AL_mpc.GraphedMPC(make(), (x0, C, c), dyn, x_init=x_ref, u_init=u_ref)
+
+        def graphed(on):
+            x, u = graphs[on](x0, C, c)
+            torch.autograd.grad(x.double().sum() + 2.0 * u.double().sum(), (C, c))
+
+        row = {"robot": robot, "T": T, "B": B}
+        # launches and device time of the forward solve, one traced call per variant
+        for on in (False, True):
+            set_switch(on)
+            eager()
+            torch.cuda.synchronize()
+            ctrl.reinitialize(x0, ctrl.mask)
+            ctrl.x_init, ctrl.u_init = x_ref, u_ref
+            with _lib.trace() as tr:
+                ctrl(x0, al_utils.QuadCost(C, c), dyn, dyn.jac)
+            key = "fused" if on else "multi"
+            row[key + "_launches"] = len(tr.records)
+            row[key + "_kernel_ms_sum"] = sum(ms for _, ms in tr.records)
+            row[key + "_kernels"] = {k.split("(")[0][-60:]: (n, round(ms, 5)) for k, (n, ms) in tr.by_kernel().items()}
+        for mode in ("eager", "graph"):
+            times = {False: [], True: []}
+            for on in (False, True):            # warm-up of both variants
+                set_switch(on)
+                for _ in range(args.block):
+                    eager() if mode == "eager" else graphed(on)
+            torch.cuda.synchronize()
+            for _ in range(args.reps):          # alternate the variants block by block
+                for on in (False, True):
+                    set_switch(on)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.block):
+                        eager() if mode == "eager" else graphed(on)
+                    torch.cuda.synchronize()
+                    times[on].append((time.perf_counter() - t0) / args.block * 1e3)
+            for on in (False, True):
+                q = statistics.quantiles(times[on], n=4)
+                key = "%s_%s_ms" % (mode, "fused" if on else "multi")
+                row[key] = {"median": statistics.median(times[on]), "q1": q[0], "q3": q[2]}
+        set_switch(False)
+        result["rows"].append(row)
+        print("%-15s T=%-3d B=%-5d | eager multi %.3f fused %.3f ms | graph multi %.3f fused %.3f ms | launches %d -> %d, "
+              "kernel time %.3f -> %.3f ms" % (robot, T, B, row["eager_multi_ms"]["median"], row["eager_fused_ms"]["median"],
+                                                row["graph_multi_ms"]["median"], row["graph_fused_ms"]["median"],
+                                                row["multi_launches"], row["fused_launches"], row["multi_kernel_ms_sum"],
+                                                row["fused_kernel_ms_sum"]), flush=True)
+    AL_mpc.PERSISTENT_SOLVE = False
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+    print(json.dumps({"rows": len(result["rows"])}))
+
+
+if __name__ == "__main__":
+    main()
