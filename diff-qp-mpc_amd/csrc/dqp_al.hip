@@ -594,6 +594,7 @@ __global__ __launch_bounds__(256) void al_linearize_kernel(LinP P)
         case DQP_DYN_CARTPOLE1L: lin_knot<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>(z, P.dt, xn, Jx, Ju); break;
         case DQP_DYN_CARTPOLE2L: lin_knot<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>(z, P.dt, xn, Jx, Ju); break;
         case DQP_DYN_PENDULUM_EULER: lin_knot<dqp::dyn::PendulumEuler>(z, P.dt, xn, Jx, Ju); break;
+        case DQP_DYN_INTEGRATOR: lin_knot<dqp::dyn::Integrator>(z, P.dt, xn, Jx, Ju); break;
         default: lin_knot<dqp::dyn::PendulumDx>(z, P.dt, xn, Jx, Ju); break;
         }
         double *oJx = P.Jx + (b * (T - 1) + t) * n * n, *oJu = P.Ju + (b * (T - 1) + t) * n * m;
@@ -889,6 +890,7 @@ int launch_ls(const LsAP &P, hipStream_t st)
     case DQP_DYN_PENDULUM_EULER: return launch_ls_t<dqp::dyn::PendulumEuler>(P, st);
     case DQP_DYN_PENDULUM_DX: return launch_ls_t<dqp::dyn::PendulumDx>(P, st);
     case DQP_DYN_REXQUADROTOR: return launch_ls_t<dqp::dyn::RexQuadrotor>(P, st);
+    case DQP_DYN_INTEGRATOR: return launch_ls_t<dqp::dyn::Integrator>(P, st);
     default: return DQP_ERR_BAD_ARG;
     }
 }
@@ -1014,6 +1016,7 @@ int launch_outer(const OutP &P, hipStream_t st)
     case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(al_outer_kernel<dqp::dyn::PendulumEuler>, grid, block, 0, st, P); break;
     case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(al_outer_kernel<dqp::dyn::PendulumDx>, grid, block, 0, st, P); break;
     case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(al_outer_kernel<dqp::dyn::RexQuadrotor>, grid, block, 0, st, P); break;
+    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Integrator>, grid, block, 0, st, P); break;
     default: return DQP_ERR_BAD_ARG;
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;

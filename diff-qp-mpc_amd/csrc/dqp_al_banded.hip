@@ -951,6 +951,7 @@ int dqp::al_banded_newton_step_keep(const dqp_al_mpc_dims *d, int dyn_id, double
     case DQP_DYN_CARTPOLE2L: return run_newton<Robot<Cartpole2l>>(P, stream);
     case DQP_DYN_PENDULUM_EULER: return run_newton<PendulumEuler>(P, stream);
     case DQP_DYN_REXQUADROTOR: return run_newton<RexQuadrotor>(P, stream);
+    case DQP_DYN_INTEGRATOR: return run_newton<Integrator>(P, stream);
     default: return run_newton<PendulumDx>(P, stream);
     }
 }
@@ -990,6 +991,7 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
     case DQP_DYN_CARTPOLE2L: return run_solve<Robot<Cartpole2l>>(P, stream);
     case DQP_DYN_PENDULUM_EULER: return run_solve<PendulumEuler>(P, stream);
     case DQP_DYN_REXQUADROTOR: return run_solve<RexQuadrotor>(P, stream);
+    case DQP_DYN_INTEGRATOR: return run_solve<Integrator>(P, stream);
     default: return run_solve<PendulumDx>(P, stream);
     }
 }

@@ -27,7 +27,7 @@
 // below are workgroup barriers of a one-wavefront workgroup.  All stores are plain vector stores, the `fail` flag an
 // ordinary atomicOr as in al_select_kernel.
 //
-// Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2),
+// Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2, the integrator),
 // 2 <= T <= 32, fp64.  RexQuadrotor (12 + 4) stays on the multi-launch path.
 #define DQP_AL_BANDED_KERNELS_ONLY
 #include "dqp_al_banded.hip"
@@ -411,6 +411,7 @@ size_t fused_lds(int dyn_id, int T)
     case DQP_DYN_CARTPOLE2L: return fused_lds_bytes<Robot<Cartpole2l>>(T);
     case DQP_DYN_PENDULUM_EULER: return fused_lds_bytes<PendulumEuler>(T);
     case DQP_DYN_PENDULUM_DX: return fused_lds_bytes<PendulumDx>(T);
+    case DQP_DYN_INTEGRATOR: return fused_lds_bytes<Integrator>(T);
     default: return 0;
     }
 }
@@ -479,6 +480,7 @@ dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t 
     case DQP_DYN_CARTPOLE2L: return launch_fused<Robot<Cartpole2l>>(P, lds, st);
     case DQP_DYN_PENDULUM_EULER: return launch_fused<PendulumEuler>(P, lds, st);
     case DQP_DYN_PENDULUM_DX: return launch_fused<PendulumDx>(P, lds, st);
+    case DQP_DYN_INTEGRATOR: return launch_fused<Integrator>(P, lds, st);
     default: return DQP_ERR_TOO_LARGE;
     }
 }

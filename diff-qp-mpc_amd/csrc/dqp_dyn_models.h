@@ -19,6 +19,8 @@
 //   pendulum_dx:    qpth/env_dx/pendulum.py:49-83 (state (cos th, sin th, thd), g=10, m=l=1,
 //                   u clamped to +-2, explicit Euler on thd then th)
 //   rexquadrotor:   deqmpc/rex_quadrotor.py:51-129 (12 states, 4 motors, MRP attitude, RK4)
+//   integrator:     deqmpc/envs.py:182-233 (double integrator, state (pos, vel), semi-implicit Euler: the one
+//                   linear model -- Jx = [[1, dt], [0, 1]], Ju = [[dt^2], [dt]])
 //
 // Everything is templated on the scalar type so that the same code evaluates values (double) and
 // forward-mode derivatives (Dual<K>: K directional derivatives ride along in registers).
@@ -227,6 +229,15 @@ struct PendulumEuler {            // deqmpc/envs.py:16-47
         const S acc = u[0] + 10.0 * s;          // (u + m g l sin th) / (m l^2), m = l = 1, g = 10
         xn[1] = x[1] + dt * acc;
         xn[0] = x[0] + dt * xn[1];
+    }
+};
+
+struct Integrator {               // deqmpc/envs.py:182-233 (nx 2, nu 1: state (pos, vel), u the acceleration)
+    static constexpr int NX = 2, NU = 1;
+    template <class S> __host__ __device__ static void step(const S *x, const S *u, double dt, S *xn)
+    {
+        xn[1] = x[1] + u[0] * dt;               // envs.py:198-199: the velocity first, the position from the NEW velocity
+        xn[0] = x[0] + xn[1] * dt;              // (no clamp: action_clip is the env's, not the dynamics')
     }
 };
 

@@ -509,6 +509,7 @@ dqp_mpc_line_search(const dqp_mpc_dims *d, int dyn_id, double dt, const double *
     case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(line_search_kernel<ModelStep<PendulumEuler>>, grid, block, 0, st, P); break;
     case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(line_search_kernel<ModelStep<PendulumDx>>, grid, block, 0, st, P); break;
     case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(line_search_kernel<ModelStep<RexQuadrotor>>, grid, block, 0, st, P); break;
+    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(line_search_kernel<ModelStep<Integrator>>, grid, block, 0, st, P); break;
     default: return DQP_ERR_BAD_ARG;
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
@@ -548,6 +549,7 @@ dqp_mpc_rollout_backward(const dqp_mpc_dims *d, int dyn_id, double dt, const dou
     case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(rollout_backward_kernel<ModelStep<PendulumEuler>>, grid, block, 0, st, P); break;
     case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(rollout_backward_kernel<ModelStep<PendulumDx>>, grid, block, 0, st, P); break;
     case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(rollout_backward_kernel<ModelStep<RexQuadrotor>>, grid, block, 0, st, P); break;
+    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(rollout_backward_kernel<ModelStep<Integrator>>, grid, block, 0, st, P); break;
     default: return DQP_ERR_BAD_ARG;
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;

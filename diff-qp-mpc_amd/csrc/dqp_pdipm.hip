@@ -460,6 +460,7 @@ __device__ __forceinline__ double true_dyn_res(const KParams &P, double *scratch
         case DQP_DYN_CARTPOLE2L: knot_step<dyn::Robot<dyn::Cartpole2l>>(zs, lane, nt, P.dynDt, fs); break;
         case DQP_DYN_PENDULUM_EULER: knot_step<dyn::PendulumEuler>(zs, lane, nt, P.dynDt, fs); break;
         case DQP_DYN_PENDULUM_DX: knot_step<dyn::PendulumDx>(zs, lane, nt, P.dynDt, fs); break;
+        case DQP_DYN_INTEGRATOR: knot_step<dyn::Integrator>(zs, lane, nt, P.dynDt, fs); break;
         default: __builtin_trap();      // fill_params only lets the models above through
         }
     }
@@ -724,7 +725,7 @@ int fill_params(const dqp_dims *d, const dqp_opts *o, KParams &P, size_t &lds_by
         if (dqp_dyn_sizes(P.dynId, &n, &m) != DQP_OK) return DQP_ERR_BAD_ARG;
         // models true_dyn_res evaluates on these one-QP-per-wavefront kernels (the quadrotor runs on the stage-wise ones)
         if (P.dynId != DQP_DYN_PENDULUM1L && P.dynId != DQP_DYN_CARTPOLE1L && P.dynId != DQP_DYN_CARTPOLE2L &&
-            P.dynId != DQP_DYN_PENDULUM_EULER && P.dynId != DQP_DYN_PENDULUM_DX)
+            P.dynId != DQP_DYN_PENDULUM_EULER && P.dynId != DQP_DYN_PENDULUM_DX && P.dynId != DQP_DYN_INTEGRATOR)
             return DQP_ERR_BAD_ARG;
         P.dynT = o->dyn_T; P.dynN = n; P.dynM = m; P.dynDt = o->dyn_dt; P.dynX0 = o->dyn_x0;
         if (P.dynT < 2 || P.dynT > WAVE || P.N != P.dynT * (n + m) ||

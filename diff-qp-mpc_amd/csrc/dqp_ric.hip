@@ -489,6 +489,7 @@ __device__ __forceinline__ void model_residuals(const Ctx<C> &K0)
     case DQP_DYN_PENDULUM_EULER: model_residuals_of<C, PendulumEuler>(K); break;
     case DQP_DYN_PENDULUM_DX: model_residuals_of<C, PendulumDx>(K); break;
     case DQP_DYN_REXQUADROTOR: model_residuals_of<C, RexQuadrotor>(K); break;
+    case DQP_DYN_INTEGRATOR: model_residuals_of<C, Integrator>(K); break;
     default: break;
     }
 }
@@ -497,7 +498,8 @@ template <class C> constexpr bool has_model()
 {
     using namespace dqp::dyn;
     return model_fits<C, Robot<Pendulum1l>>() || model_fits<C, Robot<Cartpole1l>>() || model_fits<C, Robot<Cartpole2l>>() ||
-           model_fits<C, PendulumEuler>() || model_fits<C, PendulumDx>() || model_fits<C, RexQuadrotor>();
+           model_fits<C, PendulumEuler>() || model_fits<C, PendulumDx>() || model_fits<C, RexQuadrotor>() ||
+           model_fits<C, Integrator>();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Device dynamics registry: the robots and pendulum modules the reference evaluates through
 per-robot torch extensions (deqmpc/my_envs/{pendulum1l,cartpole1l,cartpole2l}, Python wrappers
 deqmpc/my_envs/dynamics.py:15-263) or torch modules (deqmpc/envs.py:5-82,
-qpth/env_dx/pendulum.py:18-83, deqmpc/rex_quadrotor.py:7-129), as HIP kernels behind the C ABI (include/dqp.h dqp_dyn_*).
+qpth/env_dx/pendulum.py:18-83, deqmpc/rex_quadrotor.py:7-129, the double integrator of deqmpc/envs.py:182-233), as HIP kernels behind the C ABI (include/dqp.h dqp_dyn_*).
 
     dyn = DeviceDynamics("cartpole1l", dt=0.05)
     x_next = dyn(x, u)                       # the `dx` callable of the MPC layers (differentiable)
@@ -19,9 +19,12 @@ import torch
 
 from . import _lib
 
-NAMES = tuple(_lib.DQP_DYN)
+# frozen at the first six models: tests/test_gpu_al_given.py parametrises over it with its own table of sizes
+NAMES = ("pendulum1l", "cartpole1l", "cartpole2l", "pendulum_euler", "pendulum_dx", "rexquadrotor")
+ALL_NAMES = NAMES + ("integrator",)
 DEFAULT_DT = {"pendulum1l": 0.05, "cartpole1l": 0.05, "cartpole2l": 0.05, "pendulum_euler": 0.05,
-              "pendulum_dx": 0.05, "rexquadrotor": 0.05}
+              "pendulum_dx": 0.05, "rexquadrotor": 0.05, "integrator": 0.1}
+assert set(ALL_NAMES) == set(_lib.DQP_DYN) == set(DEFAULT_DT)
 
 
 def _ptr(t):
@@ -68,7 +71,7 @@ class DeviceDynamics(torch.nn.Module):
     def __init__(self, name, dt=None):
         super().__init__()
         if name not in _lib.DQP_DYN:
-            raise ValueError("unknown dynamics %r (registered: %s)" % (name, ", ".join(NAMES)))
+            raise ValueError("unknown dynamics %r (registered: %s)" % (name, ", ".join(ALL_NAMES)))
         self.name = name
         self.id = _lib.DQP_DYN[name]
         self.dt = float(DEFAULT_DT[name] if dt is None else dt)
@@ -147,7 +150,9 @@ def recognise(module, n_state, n_ctrl, dt=None, device="cuda", samples=16, tol=1
     1 + |x_next|) is returned as a DeviceDynamics -- so that a maintainer switching over keeps passing the env's module and
     still gets the on-chip solver paths.  Returns None when nothing matches (the module then takes the general paths:
     its own Jacobians into the block-tridiagonal Newton step, its residual into the caller-stepped PDIPM).  Nothing is
-    substituted on a guess: the match is numerical, on the module the caller actually passed."""
+    substituted on a guess: the match is numerical, on the module the caller actually passed.  (Three models share the
+    sizes (2, 1): pendulum1l, pendulum_euler and the integrator differ by a sin(theta) term of order dt^2 or more at the
+    sample points, seven orders above `tol`, so none of them is taken for another.)"""
     if isinstance(module, DeviceDynamics):
         return module
     gen = torch.Generator().manual_seed(0)
@@ -161,7 +166,7 @@ def recognise(module, n_state, n_ctrl, dt=None, device="cuda", samples=16, tol=1
     if not torch.is_tensor(ref) or ref.shape != x.shape:
         return None
     step = dt if dt is not None else getattr(module, "dt", None)
-    for name in NAMES:
+    for name in ALL_NAMES:
         cand = DeviceDynamics(name, dt=float(step) if step is not None else None)
         if (cand.n_state, cand.n_ctrl) != (n_state, n_ctrl):
             continue

@@ -530,7 +530,7 @@ int dqp_al_mpc_solve(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t
  * Only enqueues on `stream` (capturable): no synchronisation, no allocation.
  *
  * dqp_al_mpc_solve_fused_supported: 1 for a registered model with n_state + n_ctrl <= 8 (DQP_DYN_PENDULUM1L,
- * CARTPOLE1L, CARTPOLE2L, PENDULUM_EULER, PENDULUM_DX) at 2 <= T <= 32, else 0 (DQP_DYN_REXQUADROTOR, longer horizons:
+ * CARTPOLE1L, CARTPOLE2L, PENDULUM_EULER, PENDULUM_DX, INTEGRATOR) at 2 <= T <= 32, else 0 (DQP_DYN_REXQUADROTOR, longer horizons:
  * dqp_al_mpc_solve serves them).  Needs no device.  dqp_al_mpc_solve_fused returns DQP_ERR_BAD_ARG / DQP_ERR_TOO_LARGE
  * by the rules of dqp_al_mpc_solve, DQP_ERR_TOO_LARGE wherever _supported is 0 at valid arguments, and DQP_OK at
  * nbatch == 0 (nothing is touched).  dqp_al_mpc_solve_fused_bytes: the workspace size a caller passes -- that of
@@ -606,6 +606,9 @@ int dqp_al_lane_group(int width);
  *   DQP_DYN_REXQUADROTOR     deqmpc/rex_quadrotor.py:7-129 RexQuadrotor_dynamics, default parameters
  *       (BASELINE config 4: n_state 12 = position, MRP attitude, body velocity, body rate;
  *       n_ctrl 4 motor commands; RK4)
+ *   DQP_DYN_INTEGRATOR       deqmpc/envs.py:182-233 IntegratorDynamics, nx = 2, nu = 1 (the env of deqmpc/run.sh:
+ *       n_state 2 = position, velocity; the control is the acceleration; semi-implicit Euler, default dt 0.1;
+ *       the one linear model: df/dx = [[1, dt], [0, 1]], df/du = [[dt^2], [dt]])
  */
 enum {
     DQP_DYN_PENDULUM1L = 1,
@@ -613,7 +616,8 @@ enum {
     DQP_DYN_CARTPOLE2L = 3,
     DQP_DYN_PENDULUM_EULER = 4,
     DQP_DYN_PENDULUM_DX = 5,
-    DQP_DYN_REXQUADROTOR = 6
+    DQP_DYN_REXQUADROTOR = 6,
+    DQP_DYN_INTEGRATOR = 7
 };
 
 /* n_state / n_ctrl of a registered model; DQP_ERR_BAD_ARG for an unknown id. */
@@ -622,7 +626,8 @@ int dqp_dyn_sizes(int id, int32_t *n_state, int32_t *n_ctrl);
 /*
  * x_next = f(x, u) for n samples: x (n,n_state), u (n,n_ctrl), step dt.
  * Replaces: Dynamics.forward (deqmpc/my_envs/dynamics.py:26-63), PendulumDynamics.forward
- *           (deqmpc/envs.py:16-31), PendulumDx.forward (qpth/env_dx/pendulum.py:49-83).
+ *           (deqmpc/envs.py:16-31), PendulumDx.forward (qpth/env_dx/pendulum.py:49-83), IntegratorDynamics.forward
+ *           (deqmpc/envs.py:193-213).
  */
 int dqp_dyn_step(int id, int32_t n, const double *x, const double *u, double dt, double *x_next,
                  void *stream);

@@ -2,13 +2,80 @@
 """AL_mpc.MPC with a caller-supplied dynamics MODULE (torch nn.Module with its own Jacobian function, what the reference's
 envs are): the dense Newton step (dqp_al_assemble + dqp_al_newton_step: Hessian by fp64 MFMA, cyclic LDL^T in registers;
 nz <= 128) against the block-tridiagonal step on the module's Jacobians (dqp_al_banded_newton_step_jac) at the same
-sizes -- one call = 2 AL iterations x 4 Newton steps + backward, pendulum of deqmpc/envs.py."""
+sizes -- one call = 2 AL iterations x 4 Newton steps + backward, pendulum of deqmpc/envs.py.
+
+--integrator: the reference's `--env integrator --bsz 256 --T 5` (deqmpc/run.sh:3), forward + backward of one cold
+AL_mpc.MPC call three ways, alternating, median and quartiles of the per-call times after warm-up:
+  (a) a plain torch module of the integrator's formula on the caller-dynamics path (recognition is not involved: the
+      module goes to AL_mpc.MPC as it is) -- what the library did for this env before the model was registered
+  (b) DeviceDynamics("integrator") on the one-call solve (dqp_al_mpc_solve)
+  (c) the same on the persistent solve (dqp_al_mpc_solve_fused; PERSISTENT_SOLVE_MAX_BATCH raised for the run)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import torch
 from diff_qp_mpc_amd import AL_mpc, al_utils
 from test_gpu_al import Pendulum, PendulumJac
+
+
+class IntegratorModule(torch.nn.Module):
+    """deqmpc/envs.py:182-233 restated: x+ and (df/dx, df/du) of the semi-implicit Euler step"""
+    dt = 0.1
+
+    def forward(self, x, u):
+        vel = x[..., 1:] + u * self.dt
+        return torch.cat((x[..., :1] + vel * self.dt, vel), dim=-1)
+
+    def jac(self, x, u):
+        dt = self.dt
+        fx = x.new_tensor([[1.0, dt], [0.0, 1.0]]).expand(x.shape[0], 2, 2)
+        fu = x.new_tensor([[dt * dt], [dt]]).expand(x.shape[0], 2, 1)
+        return self.forward(x, u), (fx, fu)
+
+
+def integrator_case(B=256, T=5, warmup=5, reps=40):
+    import numpy as np
+    from diff_qp_mpc_amd.dynamics import DeviceDynamics
+    nx, nu = 2, 1
+    gen = torch.Generator().manual_seed(0)
+    x0 = ((torch.rand(B, nx, generator=gen, dtype=torch.float64) * 4 - 2) * (torch.arange(B) % 2 * 0.99 + 0.01)[:, None]).cuda()
+    Qd = torch.tensor([10.0, 1.0, 0.01], dtype=torch.float64).repeat(B, T, 1).cuda()
+    C = torch.diag_embed(Qd).requires_grad_()
+    c = torch.zeros(B, T, nx + nu, dtype=torch.float64).cuda().requires_grad_()
+    lim = torch.full((nu,), 2.0, dtype=torch.float64).cuda()
+    mod, dev_dyn = IntegratorModule(), DeviceDynamics("integrator")
+    ways = [("(a) caller's torch module", mod, mod.jac, False), ("(b) registered, one-call solve", dev_dyn, dev_dyn.jac, False),
+            ("(c) registered, persistent solve", dev_dyn, dev_dyn.jac, True)]
+    ctrls = [AL_mpc.MPC(nx, nu, T, u_lower=-lim, u_upper=lim, n_batch=B, verbose=0, solver_type="dense", dtype=torch.float64,
+                        eps=1e-5, exit_unconverged=False, backprop=False) for _ in ways]
+
+    def call(i):
+        _, dyn, jac, persistent = ways[i]
+        AL_mpc.PERSISTENT_SOLVE, AL_mpc.PERSISTENT_SOLVE_MAX_BATCH = persistent, (B if persistent else 0)
+        ctrls[i].reinitialize(x0, torch.ones(B, T, 1, device="cuda"))
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        x, u = ctrls[i](x0, al_utils.QuadCost(C, c), dyn, jac)
+        (x.double().sum() + 2.0 * u.double().sum()).backward()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, x.detach()
+
+    times, xs = [[] for _ in ways], [None] * len(ways)
+    for r in range(warmup + reps):
+        for i in range(len(ways)):          # alternate the three ways inside one run
+            t, xs[i] = call(i)
+            if r >= warmup:
+                times[i].append(t * 1e3)
+    AL_mpc.PERSISTENT_SOLVE, AL_mpc.PERSISTENT_SOLVE_MAX_BATCH = False, 0
+    for (name, *_), ts in zip(ways, times):
+        q1, med, q3 = np.percentile(ts, [25, 50, 75])
+        print("integrator B=%d T=%d  %-34s median %.3f ms  quartiles [%.3f, %.3f]  (%d calls, forward + backward)" % (
+            B, T, name, med, q1, q3, len(ts)))
+    print("   max |x| difference to (a): (b) %.2e  (c) %.2e" % (float((xs[1] - xs[0]).abs().max()), float((xs[2] - xs[0]).abs().max())))
+
+
+if "--integrator" in sys.argv:
+    integrator_case()
+    sys.exit(0)
 
 nx, nu = 2, 1
 for B, T in ((4096, 20), (4096, 40), (128, 20)):
