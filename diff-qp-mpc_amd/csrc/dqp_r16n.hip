@@ -328,6 +328,43 @@ __device__ __forceinline__ void mpc_rows_A(const KParams &P, long long qp, int n
     }
 }
 
+// COUNT contiguous doubles between the caller's workspace and LDS, copied by the 16 lanes of a QP (lane r
+// takes elements r, r + 16, ...).  The trip count K is a compile-time constant and the index of a lane past
+// the end is clamped, so all K loads are issued back to back and waited for once; a loop over
+// `e = r; e < COUNT; e += 16` has a lane-dependent trip count, stays rolled and pays one full memory
+// round trip per element.  ctx_fetch issues the loads, ctx_stash writes them out (the lanes past the end
+// are masked): a caller can put a barrier between the two.
+template <int COUNT> struct CtxRegs {
+    static_assert(COUNT > 0, "nothing to copy");
+    double v[(COUNT + 15) / 16];
+};
+template <int COUNT>
+__device__ __forceinline__ void ctx_fetch(const double *src, CtxRegs<COUNT> &t, int r)
+{
+#pragma unroll
+    for (int k = 0; k < (COUNT + 15) / 16; ++k) {
+        const int e = r + 16 * k;
+        t.v[k] = src[(16 * k + 15 < COUNT || e < COUNT) ? e : COUNT - 1];
+    }
+}
+template <int COUNT>
+__device__ __forceinline__ void ctx_stash(double *dst, const CtxRegs<COUNT> &t, int r)
+{
+#pragma unroll
+    for (int k = 0; k < (COUNT + 15) / 16; ++k) {
+        const int e = r + 16 * k;
+        if (16 * k + 15 < COUNT || e < COUNT) dst[e] = t.v[k];
+    }
+}
+// the other direction (every LDS read is issued before the first global store)
+template <int COUNT>
+__device__ __forceinline__ void lds_to_ctx(const double *src, double *dst, int r)
+{
+    CtxRegs<COUNT> t;
+    ctx_fetch<COUNT>(src, t, r);
+    ctx_stash<COUNT>(dst, t, r);
+}
+
 // [Gz | W], U, tau, 1/diag(U) -> the caller's workspace (the factorisation context backward restarts
 // from).  Column-major: the 16 lanes of a QP write 16 consecutive doubles (row-major 8-byte stores
 // 240 B apart cost 5x write amplification in HBM).
@@ -471,7 +508,7 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     __syncthreads();
     if (C::EARLY) {
         double *ws = P.workspace + qp * (long long)C::wsQP;
-        for (int e = r; e < tri(N); e += 16) ws[C::wLq + e] = lds[C::oLq + e];
+        lds_to_ctx<tri(N)>(lds + C::oLq, ws + C::wLq, r);
 #pragma unroll
         for (int s = 0; s < SN; ++s)
             if (r + 16 * s < N) ws[C::wRdq + r + 16 * s] = st.rdq[s];
@@ -626,7 +663,7 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
         __builtin_amdgcn_sched_barrier(0);
         if (C::EARLY) {
             double *ws = P.workspace + qp * (long long)C::wsQP;
-            for (int e = r; e < C::tailsz; e += 16) ws[C::wTl + e] = lds[C::oTl + e];
+            lds_to_ctx<C::tailsz>(lds + C::oTl, ws + C::wTl, r);
         }
         DQP_PHASE_FENCE();
 
@@ -835,8 +872,8 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     {
         if (!C::EARLY) {
             double *ws = P.workspace + qp * (long long)C::wsQP;
-            for (int e = r; e < C::tailsz; e += 16) ws[C::wTl + e] = lds[C::oTl + e];
-            for (int e = r; e < tri(N); e += 16) ws[C::wLq + e] = lds[C::oLq + e];
+            lds_to_ctx<C::tailsz>(lds + C::oTl, ws + C::wTl, r);
+            lds_to_ctx<tri(N)>(lds + C::oLq, ws + C::wLq, r);
             if (!C::PARKWU) park_GU<C>(ws, st, r);
 #pragma unroll
             for (int s = 0; s < SN; ++s)
@@ -913,12 +950,12 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
     bool inM[SM];
 #pragma unroll
     for (int s = 0; s < SM; ++s) inM[s] = r + 16 * s < M;
-    // the reflector tails come back from the workspace into the (now idle) Gz Gz^T region
+    // the reflector tails come back from the workspace into the (now idle) Gz Gz^T region: all loads are
+    // issued ahead of the barrier that frees the region (each lane reads what it stored itself in setup)
+    CtxRegs<C::tailsz> tl;
+    if (E > 0 && reload_tails) ctx_fetch<C::tailsz>(P.workspace + qp * (long long)C::wsQP + C::wTl, tl, r);
     __syncthreads();
-    if (E > 0 && reload_tails) {
-        const double *ws = P.workspace + qp * (long long)C::wsQP + C::wTl;
-        for (int e = r; e < C::tailsz; e += 16) lds[C::oTl + e] = ws[e];
-    }
+    if (E > 0 && reload_tails) ctx_stash<C::tailsz>(lds + C::oTl, tl, r);
     __syncthreads();
 
     // recover x = Lq^-T Qf [w* ; xy],  y = U^-T (c* delta w1 - xy - py - W^T z*)
@@ -1193,8 +1230,14 @@ __device__ __forceinline__ void load_ctx(const KParams &P, long long qp, int r, 
     st.status = DQP_STATUS_OK;
     {
         const double *ws = P.workspace + qp * (long long)C::wsQP;
-        for (int e = r; e < C::tailsz; e += 16) lds[C::oTl + e] = ws[C::wTl + e];
-        for (int e = r; e < tri(N); e += 16) lds[C::oLq + e] = ws[C::wLq + e];
+        // the LDS-bound pieces in one burst of their own (51 loads at the metric size), the register-bound ones
+        // in a second: with both in flight at once the backward kernel runs out of VGPRs
+        CtxRegs<C::tailsz> tl;
+        CtxRegs<tri(N)> lq;
+        ctx_fetch<C::tailsz>(ws + C::wTl, tl, r);
+        ctx_fetch<tri(N)>(ws + C::wLq, lq, r);
+        ctx_stash<C::tailsz>(lds + C::oTl, tl, r);
+        ctx_stash<tri(N)>(lds + C::oLq, lq, r);
 #pragma unroll
         for (int s = 0; s < SM; ++s) {
             const int i = r + 16 * s, ic = i < M ? i : M - 1;
@@ -1260,12 +1303,17 @@ __global__ __launch_bounds__(64) void finish_kernel(KParams P)
     const double delta = ws[C::wDl];
     // the problem's best iteration before the stop (same rule as the kernels: first strict minimum)
     const double2 *h = reinterpret_cast<const double2 *>(P.histIn) + qp;
-    double best = h[0].x;
+    // cap <= maxIter <= 64 under the batch rule (64-bit iteration masks; the host entry points refuse more): a
+    // fixed trip count with the index clamped, so every load is in flight before the first comparison (a loop
+    // up to cap pays one memory round trip per iteration)
+    double hv[64];
+#pragma unroll
+    for (int it = 0; it < 64; ++it) hv[it] = h[(long long)(it < cap ? it : 0) * P.B].x;
+    double best = hv[0];
     int arg = 0;
-    for (int it = 1; it < cap; ++it) {
-        const double v = h[(long long)it * P.B].x;
-        if (v < best) { best = v; arg = it; }
-    }
+#pragma unroll
+    for (int it = 1; it < 64; ++it)
+        if (it < cap && hv[it] < best) { best = hv[it]; arg = it; }
     const double *sp = P.snap + ((long long)arg * P.B + qp) * C::snapDim;
     double bw[SR], bs[SM], bz[SM];
 #pragma unroll
