@@ -140,7 +140,9 @@ class MPC(Module):
         banded = al_utils.BANDED_NEWTON_AL and nt <= 16                # one knot per 16-lane DPP row
         dense = self.n_state <= 8 and self.n_ctrl <= 2 and self.T * nt <= 128
         device_path = (_fused and FUSED_NEWTON_AL and isinstance(dx, DeviceDynamics) and (banded or dense)
-                       and self.x_lower is None and self.u_lower.numel() == self.n_ctrl)
+                       and self.x_lower is None
+                       and al_utils.bounds_supported(self.u_lower, self.u_upper, x.size(0), self.T, self.n_ctrl))
+        strided = al_utils.bounds_strided(self.u_lower, self.n_ctrl)      # per-sample / per-knot bounds
         if (ONE_CALL_SOLVE and device_path and banded and al_utils.BANDED_NEWTON_AL and torch.is_tensor(self.rho_prev if rho_init is None else rho_init)
                 and dt == torch.float64):
             # the whole solve -- start cost, warm start, al_iter x [Newton steps + line search, multiplier update] -- as one
@@ -149,7 +151,7 @@ class MPC(Module):
             rho = self.rho_prev if rho_init is None else rho_init
             prev = None if self.just_initialized else self._device_history()
             persistent = (PERSISTENT_SOLVE and x.size(0) <= PERSISTENT_SOLVE_MAX_BATCH
-                          and al_utils.fused_solve_supported(x.size(0), dx, self.T))
+                          and al_utils.fused_solve_supported(x.size(0), dx, self.T, strided))
             xu, hc, hl, hr, resn, fail = al_utils.ALSolveDevice.apply(          # the iterate enters detached (AL_mpc.py:287)
                 x.detach(), u.detach(), x0.detach(), cost.C.to(dt), cost.c.to(dt), lamda.detach(), rho.detach(), dx,
                 self.u_lower, self.u_upper, self.al_iter, prev, persistent)
@@ -186,9 +188,10 @@ class MPC(Module):
                     lambda xi, Qi, qi, yi: self.merit_grad_hess(xi, Qi, qi, dx, dx_jac, x0, yi, rho_i),
                     xu, x0, lamda, rho, Qg, qg, 1e-3, 1e-6, True)
             banded_jac = (not device_path and _fused and BANDED_USER_DYNAMICS and x.is_cuda and dx_jac is not None
-                          and self.x_lower is None and self.u_lower.numel() == self.n_ctrl
+                          and self.x_lower is None
+                          and al_utils.bounds_supported(self.u_lower, self.u_upper, x.size(0), self.T, self.n_ctrl)
                           and self.T * nt > BANDED_USER_DYNAMICS_FROM_NZ
-                          and al_utils.banded_jac_supported(self.n_batch, self.n_state, self.n_ctrl, self.T))
+                          and al_utils.banded_jac_supported(self.n_batch, self.n_state, self.n_ctrl, self.T, strided))
             if banded_jac:
                 # caller-supplied dynamics at a horizon the dense Newton step cannot hold (nz > 128): its own
                 # Jacobians into the block-tridiagonal step

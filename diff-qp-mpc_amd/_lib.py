@@ -55,7 +55,11 @@ SYMBOLS = ("dqp_version", "dqp_error_string", "dqp_workspace_bytes", "dqp_termin
            "dqp_al_mpc_solve_fused_supported", "dqp_al_mpc_solve_fused_bytes", "dqp_al_mpc_solve_fused",
            "dqp_mpc_qp_stepped_workspace_bytes", "dqp_mpc_qp_stepped_termination_bytes", "dqp_mpc_qp_forward_stepped", "dqp_trace_begin", "dqp_trace_end",
            "dqp_dyn_sizes", "dqp_dyn_step", "dqp_dyn_jacobian", "dqp_dyn_forward_dynamics",
-           "dqp_dyn_forward_derivatives")
+           "dqp_dyn_forward_derivatives") + tuple(
+    # the per-sample / per-knot bound layout (dqp_al_bounds): a twin of every entry point that takes control bounds
+    s + "_bounds" for s in ("dqp_al_merit", "dqp_al_newton_solve", "dqp_al_outer_update", "dqp_al_mpc_solve",
+                            "dqp_al_mpc_solve_fused_supported", "dqp_al_mpc_solve_fused_bytes", "dqp_al_mpc_solve_fused",
+                            "dqp_al_banded_newton_step", "dqp_al_banded_newton_step_jac")) + ("dqp_al_mpc_solve_fused_lds_bytes",)
 DQP_DYN = {"pendulum1l": 1, "cartpole1l": 2, "cartpole2l": 3, "pendulum_euler": 4, "pendulum_dx": 5,
            "rexquadrotor": 6, "integrator": 7}
 
@@ -63,6 +67,12 @@ DQP_DYN = {"pendulum1l": 1, "cartpole1l": 2, "cartpole2l": 3, "pendulum_euler": 
 class dqp_al_mpc_dims(ctypes.Structure):
     _fields_ = [("nbatch", ctypes.c_int32), ("n_state", ctypes.c_int32), ("n_ctrl", ctypes.c_int32),
                 ("T", ctypes.c_int32)]
+
+
+class dqp_al_bounds(ctypes.Structure):
+    """lower / upper of (sample b, knot t, control k) at [b * stride_b + t * stride_t + k] (include/dqp.h)"""
+    _fields_ = [("lower", ctypes.c_void_p), ("upper", ctypes.c_void_p), ("stride_b", ctypes.c_int64),
+                ("stride_t", ctypes.c_int64)]
 
 
 class dqp_al_dims(ctypes.Structure):
@@ -179,6 +189,30 @@ def load():
     lib.dqp_al_mpc_solve_fused_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)]
     lib.dqp_al_mpc_solve_fused.restype = ctypes.c_int
     lib.dqp_al_mpc_solve_fused.argtypes = lib.dqp_al_mpc_solve.argtypes
+    # the _bounds twins: the (u_lower, u_upper) pointer pair becomes one dqp_al_bounds *
+    _bp, _mp = ctypes.POINTER(dqp_al_bounds), ctypes.POINTER(dqp_al_mpc_dims)
+    lib.dqp_al_merit_bounds.restype = ctypes.c_int
+    lib.dqp_al_merit_bounds.argtypes = [_mp, ctypes.c_int32] + [_dp] * 7 + [_bp] + [_dp] * 2
+    lib.dqp_al_newton_solve_bounds.restype = ctypes.c_int
+    lib.dqp_al_newton_solve_bounds.argtypes = ([_mp, ctypes.c_int, ctypes.c_double, ctypes.c_int32, ctypes.c_int32] + [_dp] * 5
+                                               + [_bp] + [_dp] * 6)
+    lib.dqp_al_outer_update_bounds.restype = ctypes.c_int
+    lib.dqp_al_outer_update_bounds.argtypes = [_mp, ctypes.c_int, ctypes.c_double] + [_dp] * 6 + [_bp] + [_dp] * 4
+    lib.dqp_al_banded_newton_step_bounds.restype = ctypes.c_int
+    lib.dqp_al_banded_newton_step_bounds.argtypes = [_mp, ctypes.c_int, ctypes.c_double] + [_dp] * 6 + [_bp] + [_dp] * 4
+    lib.dqp_al_banded_newton_step_jac_bounds.restype = ctypes.c_int
+    lib.dqp_al_banded_newton_step_jac_bounds.argtypes = [_mp] + [_dp] * 6 + [_bp] + [_dp] * 7
+    lib.dqp_al_mpc_solve_bounds.restype = ctypes.c_int
+    lib.dqp_al_mpc_solve_bounds.argtypes = ([_mp, ctypes.c_int, ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
+                                            + [_dp] * 5 + [_bp] + [_dp] * 5 + [ctypes.c_int32] + [_dp] * 10)
+    lib.dqp_al_mpc_solve_fused_bounds.restype = ctypes.c_int
+    lib.dqp_al_mpc_solve_fused_bounds.argtypes = lib.dqp_al_mpc_solve_bounds.argtypes
+    lib.dqp_al_mpc_solve_fused_supported_bounds.restype = ctypes.c_int
+    lib.dqp_al_mpc_solve_fused_supported_bounds.argtypes = [_mp, ctypes.c_int, _bp]
+    lib.dqp_al_mpc_solve_fused_bytes_bounds.restype = ctypes.c_size_t
+    lib.dqp_al_mpc_solve_fused_bytes_bounds.argtypes = [_mp, _bp]
+    lib.dqp_al_mpc_solve_fused_lds_bytes.restype = ctypes.c_size_t
+    lib.dqp_al_mpc_solve_fused_lds_bytes.argtypes = [_mp, ctypes.c_int, _bp]
     lib.dqp_al_lane_group.restype = ctypes.c_int
     lib.dqp_al_lane_group.argtypes = [ctypes.c_int]
     lib.dqp_mpc_qp_stepped_workspace_bytes.restype = ctypes.c_size_t

@@ -52,6 +52,68 @@ def _need_gpu(t):
 
 
 # ------------------------------------------------------------------------------------------
+# control bounds per sample and per knot: the layout the kernels index (include/dqp.h: dqp_al_bounds)
+# ------------------------------------------------------------------------------------------
+class DeviceBounds:
+    """Bounds as the `_bounds` entry points take them: `lower` / `upper` contiguous fp64 buffers (kept alive here) and the
+    element strides with which bound (b, t, k) sits at [b * stride_b + t * stride_t + k]; `c` is the dqp_al_bounds."""
+    __slots__ = ("lower", "upper", "stride_b", "stride_t", "c")
+
+    def __init__(self, lower, upper, stride_b, stride_t):
+        self.lower, self.upper, self.stride_b, self.stride_t = lower, upper, stride_b, stride_t
+        self.c = _lib.dqp_al_bounds(lower.data_ptr(), upper.data_ptr(), stride_b, stride_t)
+
+    def ref(self):
+        return ctypes.byref(self.c)
+
+
+def bounds_layout(u_lower, u_upper, n_batch, T, n_ctrl):
+    """-> DeviceBounds for bounds of shape (n_ctrl,), (T, n_ctrl), (B, 1, n_ctrl) or (B, T, n_ctrl) -- batch-major, as
+    AL_mpc.MPC indexes u -- without expanding them: the buffers hold n_ctrl, T n_ctrl, B n_ctrl or B T n_ctrl doubles and
+    the strides are (0, 0), (0, m), (m, 0), (T m, m).  Raises ValueError for anything else: lower / upper of different
+    shapes, a time-major (T, B, n_ctrl) array, scalars.  fp64 contiguous tensors are passed through as they are (no
+    copy, nothing allocated -- a captured call keeps its pointers), others are converted once per call."""
+    strides = _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl)
+    d64 = lambda t: t.detach().double().contiguous()
+    if strides == (0, 0):
+        return DeviceBounds(d64(u_lower).reshape(-1), d64(u_upper).reshape(-1), 0, 0)
+    return DeviceBounds(d64(u_lower), d64(u_upper), *strides)
+
+
+def _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl):
+    """(stride_b, stride_t) of bounds_layout from the shapes alone; ValueError where it has none"""
+    if not (torch.is_tensor(u_lower) and torch.is_tensor(u_upper)):
+        raise ValueError("control bounds must be tensors")
+    if u_lower.shape != u_upper.shape:
+        raise ValueError("u_lower %s and u_upper %s differ in shape" % (tuple(u_lower.shape), tuple(u_upper.shape)))
+    shp, m = tuple(u_lower.shape), n_ctrl
+    if u_lower.numel() == m:            # the vector, in whatever shape holds n_ctrl numbers (as before)
+        return (0, 0)
+    if shp == (T, m):
+        return (0, m)
+    if shp == (n_batch, 1, m):
+        return (m, 0)
+    if shp == (n_batch, T, m):
+        return (T * m, m)
+    raise ValueError("control bounds of shape %s: expected (n_ctrl,), (T, n_ctrl), (B, 1, n_ctrl) or (B, T, n_ctrl) "
+                     "with B = %d, T = %d, n_ctrl = %d (batch-major)" % (shp, n_batch, T, m))
+
+
+def bounds_supported(u_lower, u_upper, n_batch, T, n_ctrl):
+    """The device AL paths take these bounds (bounds_layout accepts them)."""
+    try:
+        _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl)
+    except ValueError:
+        return False
+    return True
+
+
+def bounds_strided(u_lower, n_ctrl):
+    """per-sample / per-knot bounds (anything but the n_ctrl-vector)"""
+    return torch.is_tensor(u_lower) and u_lower.numel() != n_ctrl
+
+
+# ------------------------------------------------------------------------------------------
 # residuals and Jacobians of  x_{t+1} = f(x_t, u_t), x_0 = x0, u_lower <= u <= u_upper
 # ------------------------------------------------------------------------------------------
 def _split(xu, n_state):
@@ -185,14 +247,20 @@ def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_up
     """cost + rho/2 |res_clamp|^2 + lamda . res; a leading candidate axis (n_ls,B,T,nt) is
     folded into the batch (al_utils.py:37-59)."""
     m_ctrl = xu.shape[-1] - x0.shape[-1]
-    if (xu.is_cuda and not torch.is_grad_enabled() and torch.is_tensor(u_lower) and u_lower.dim() == 1
-            and torch.is_tensor(u_upper) and u_lower.numel() == m_ctrl and u_upper.numel() == m_ctrl
-            and x_lower is None and x_upper is None):   # the kernel reads n_ctrl bounds per knot
+    if (xu.is_cuda and not torch.is_grad_enabled() and x_lower is None and x_upper is None
+            and bounds_supported(u_lower, u_upper, x0.shape[0], xu.shape[-2], m_ctrl)    # a layout the kernel takes
+            and (u_lower.dim() == 1 or bounds_strided(u_lower, m_ctrl))):
         return _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper)
     if xu.dim() == 4:
         k, B = xu.shape[:2]
         rep = lambda t: t[None].expand(k, *t.shape).reshape(k * B, *t.shape[1:])
         xu, x0, Q, q, rho, lamda = xu.reshape(k * B, *xu.shape[2:]), rep(x0), rep(Q), rep(q), rep(rho), rep(lamda)
+        # per-sample bounds follow their sample through the candidate axis
+        per_sample = lambda t: torch.is_tensor(t) and t.dim() == 3 and t.shape[0] == B and B > 1
+        if per_sample(u_lower):
+            u_lower = rep(u_lower)
+        if per_sample(u_upper):
+            u_upper = rep(u_upper)
     B = xu.shape[0]
     res, resc = dyn_res(xu, dx, x0, x_lower, x_upper, u_lower, u_upper)
     return compute_cost(xu, Q, q) + 0.5 * rho[:, 0] * (resc * resc).sum(1) + (lamda * res).sum(1)
@@ -219,11 +287,12 @@ def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper):
     # the converted inputs must outlive the launch: a temporary freed right after data_ptr() is
     # handed back to the caching allocator and overwritten by the NEXT conversion before the
     # kernel (enqueued after all of them) reads it
-    keep = [d64(x0), d64(Q), d64(q), d64(lamda), d64(rho).reshape(B), d64(u_lower), d64(u_upper)]
+    keep = [d64(x0), d64(Q), d64(q), d64(lamda), d64(rho).reshape(B)]
+    bd = bounds_layout(u_lower, u_upper, B, T, m)
     with torch.cuda.device(xu.device):
-        rc = lib.dqp_al_merit(ctypes.byref(dims), k, _ptr(xu64), _ptr(xn64), *[_ptr(t) for t in keep],
-                              _ptr(merit), _stream(xu.device))
-    _lib.check(rc, "dqp_al_merit")
+        rc = lib.dqp_al_merit_bounds(ctypes.byref(dims), k, _ptr(xu64), _ptr(xn64), *[_ptr(t) for t in keep], bd.ref(),
+                                     _ptr(merit), _stream(xu.device))
+    _lib.check(rc, "dqp_al_merit_bounds")
     return merit.to(xu.dtype)
 
 
@@ -392,11 +461,15 @@ class NewtonAL(torch.autograd.Function):
         return (None,) * 8 + (g * x, g, None, None, None)
 
 
-def banded_jac_supported(B, n, m, T):
+def banded_jac_supported(B, n, m, T, strided=False):
     """A block-tridiagonal Newton step exists for caller-linearised dynamics of these sizes (n + m <= 16: 8- / 16-lane
-    kernels; the wide pairs up to n + m = 32: one problem per half-wavefront)."""
+    kernels; the wide pairs up to n + m = 32: one problem per half-wavefront).  `strided`: with per-sample / per-knot
+    bounds, which the wide pairs do not take."""
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
-    return int(_lib.load().dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) > 0
+    lib = _lib.load()
+    if strided:         # dqp_al_banded_factor_bytes(dims, 0) is 0 at the wide pairs
+        return int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), 0)) > 0
+    return int(lib.dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) > 0
 
 
 class NewtonALBandedJac(torch.autograd.Function):
@@ -417,7 +490,8 @@ class NewtonALBandedJac(torch.autograd.Function):
         d64 = lambda t: t.detach().double().contiguous()
         dims = _lib.dqp_al_mpc_dims(B, n, m, T)
         rho_t = rho if torch.is_tensor(rho) else torch.full((B,), float(rho), **kw)
-        keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho_t).reshape(B), d64(u_lower).reshape(-1), d64(u_upper).reshape(-1)]
+        keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho_t).reshape(B)]
+        bd = bounds_layout(u_lower, u_upper, B, T, m)
         fac = torch.empty(int(lib.dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) // 8, **kw)
         upd = torch.empty(B, T, nt, **kw)
         info = torch.empty(B, dtype=torch.int32, device=dev)
@@ -433,11 +507,11 @@ class NewtonALBandedJac(torch.autograd.Function):
                 x_next, (Jx, Ju) = dx_jac(xs, us)
             hold = [d64(x_next), d64(Jx), d64(Ju)]
             with torch.cuda.device(dev):
-                rc = lib.dqp_al_banded_newton_step_jac(ctypes.byref(dims), _ptr(xu), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]),
-                                                       _ptr(keep[3]), _ptr(keep[4]), _ptr(keep[5]), _ptr(keep[6]),
-                                                       _ptr(hold[0]), _ptr(hold[1]), _ptr(hold[2]), _ptr(upd), _ptr(fac),
-                                                       _ptr(info), _stream(dev))
-            _lib.check(rc, "dqp_al_banded_newton_step_jac")
+                rc = lib.dqp_al_banded_newton_step_jac_bounds(ctypes.byref(dims), _ptr(xu), _ptr(keep[0]), _ptr(keep[1]),
+                                                              _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4]), bd.ref(),
+                                                              _ptr(hold[0]), _ptr(hold[1]), _ptr(hold[2]), _ptr(upd), _ptr(fac),
+                                                              _ptr(info), _stream(dev))
+            _lib.check(rc, "dqp_al_banded_newton_step_jac_bounds")
             if bool((info != 0).any()):     # a pivot was not positive: the reference switches to an LU solve
                 failed = True               # (al_utils.py:419-427); here the caller re-runs the dense path
                 break
@@ -482,7 +556,8 @@ class NewtonALDevice(torch.autograd.Function):
         dev = xi.device
         d64 = lambda t: t.detach().double().contiguous()
         xu = d64(xi).clone()
-        keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho).reshape(B), d64(u_lower).reshape(-1), d64(u_upper).reshape(-1)]
+        keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho).reshape(B)]
+        bd = bounds_layout(u_lower, u_upper, B, T, m)
         dims = _lib.dqp_al_mpc_dims(B, n, m, T)
         kw = dict(dtype=torch.float64, device=dev)
         banded = 1 if BANDED_NEWTON_AL else 0
@@ -494,10 +569,10 @@ class NewtonALDevice(torch.autograd.Function):
         fail = torch.zeros(1, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_newton_solve_bytes(ctypes.byref(dims), banded)) // 8 + 1, **kw)
         with torch.cuda.device(dev):
-            rc = lib.dqp_al_newton_solve(ctypes.byref(dims), dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded,
-                                         *[_ptr(t) for t in keep], _ptr(xu), _ptr(L), _ptr(status), _ptr(fail),
-                                         _ptr(ws), _stream(dev))
-        _lib.check(rc, "dqp_al_newton_solve")
+            rc = lib.dqp_al_newton_solve_bounds(ctypes.byref(dims), dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded,
+                                                *[_ptr(t) for t in keep], bd.ref(), _ptr(xu), _ptr(L), _ptr(status),
+                                                _ptr(fail), _ptr(ws), _stream(dev))
+        _lib.check(rc, "dqp_al_newton_solve_bounds")
         ctx.slow_ctx = None
         if fail_sink is not None:           # the caller checks all flags once, at the end of its solve
             fail_sink.append(fail)
@@ -548,8 +623,9 @@ class ALSolveDevice(torch.autograd.Function):
         nt, ncon = n + m, T * n + 2 * T * m
         dev = x0.device
         d64 = lambda t: t.detach().double().contiguous()
-        keep = [d64(x_init), d64(u_init), d64(x0), d64(Q), d64(q), d64(u_lower).reshape(-1), d64(u_upper).reshape(-1),
-                d64(lam), d64(rho).reshape(B)]
+        keep = [d64(x_init), d64(u_init), d64(x0), d64(Q), d64(q)]
+        keep2 = [d64(lam), d64(rho).reshape(B)]
+        bd = bounds_layout(u_lower, u_upper, B, T, m)
         _need_gpu(keep[0])
         pc, pl, pr = (d64(t) for t in prev) if prev is not None else (None, None, None)
         n_prev = pc.shape[0] if prev is not None else 0
@@ -561,10 +637,11 @@ class ALSolveDevice(torch.autograd.Function):
         L = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), dyn.id)) // 8, **kw)
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8 + 1, **kw)
-        entry, name = (lib.dqp_al_mpc_solve_fused, "dqp_al_mpc_solve_fused") if fused else (lib.dqp_al_mpc_solve, "dqp_al_mpc_solve")
+        entry, name = ((lib.dqp_al_mpc_solve_fused_bounds, "dqp_al_mpc_solve_fused_bounds") if fused
+                       else (lib.dqp_al_mpc_solve_bounds, "dqp_al_mpc_solve_bounds"))
         with torch.cuda.device(dev):
-            rc = entry(ctypes.byref(dims), dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *[_ptr(t) for t in keep],
-                       _ptr(pc), _ptr(pl), _ptr(pr), n_prev, _ptr(xu), _ptr(hc), _ptr(hl), _ptr(hr), _ptr(resn),
+            rc = entry(ctypes.byref(dims), dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *[_ptr(t) for t in keep], bd.ref(),
+                       *[_ptr(t) for t in keep2], _ptr(pc), _ptr(pl), _ptr(pr), n_prev, _ptr(xu), _ptr(hc), _ptr(hl), _ptr(hr), _ptr(resn),
                        _ptr(L), _ptr(status), _ptr(fail), _ptr(ws), _stream(dev))
         _lib.check(rc, name)
         ctx.dims, ctx.dyn_id = dims, dyn.id
@@ -583,9 +660,14 @@ class ALSolveDevice(torch.autograd.Function):
         return (None,) * 3 + (g * x, g) + (None,) * 8                      # al_utils.py:482-485
 
 
-def fused_solve_supported(n_batch, dyn, T):
-    """dqp_al_mpc_solve_fused exists for this registered model and horizon (n_state + n_ctrl <= 8, 2 <= T <= 32)"""
+def fused_solve_supported(n_batch, dyn, T, strided=False):
+    """dqp_al_mpc_solve_fused exists for this registered model and horizon (n_state + n_ctrl <= 8, 2 <= T <= 32);
+    `strided`: with per-sample / per-knot bounds, whose 2 T n_ctrl doubles are staged in LDS next to the problem"""
     dims = _lib.dqp_al_mpc_dims(n_batch, dyn.n_state, dyn.n_ctrl, T)
+    if strided:
+        m = dyn.n_ctrl
+        bd = _lib.dqp_al_bounds(None, None, T * m, m)
+        return bool(_lib.load().dqp_al_mpc_solve_fused_supported_bounds(ctypes.byref(dims), dyn.id, ctypes.byref(bd)))
     return bool(_lib.load().dqp_al_mpc_solve_fused_supported(ctypes.byref(dims), dyn.id))
 
 
@@ -595,14 +677,15 @@ def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper):
     B, T, nt = xu.shape
     dev = xu.device
     d64 = lambda t: t.detach().double().contiguous()
-    keep = [d64(xu), d64(x0), d64(lam), d64(rho).reshape(B), d64(Q), d64(q), d64(u_lower).reshape(-1), d64(u_upper).reshape(-1)]
+    keep = [d64(xu), d64(x0), d64(lam), d64(rho).reshape(B), d64(Q), d64(q)]
+    bd = bounds_layout(u_lower, u_upper, B, T, dyn.n_ctrl)
     kw = dict(dtype=torch.float64, device=dev)
     lam_new, cost, resn = torch.empty_like(keep[2]), torch.empty(B, **kw), torch.empty(B, **kw)
     dims = _lib.dqp_al_mpc_dims(B, dyn.n_state, dyn.n_ctrl, T)
     with torch.cuda.device(dev):
-        rc = lib.dqp_al_outer_update(ctypes.byref(dims), dyn.id, dyn.dt, *[_ptr(t) for t in keep], _ptr(lam_new),
-                                     _ptr(cost), _ptr(resn), _stream(dev))
-    _lib.check(rc, "dqp_al_outer_update")
+        rc = lib.dqp_al_outer_update_bounds(ctypes.byref(dims), dyn.id, dyn.dt, *[_ptr(t) for t in keep], bd.ref(),
+                                            _ptr(lam_new), _ptr(cost), _ptr(resn), _stream(dev))
+    _lib.check(rc, "dqp_al_outer_update_bounds")
     return lam_new.to(lam.dtype), cost.to(xu.dtype), resn.to(xu.dtype)
 
 

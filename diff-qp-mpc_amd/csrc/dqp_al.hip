@@ -20,15 +20,21 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/dqp.h"
 #include "dqp_r16_prims.h"
 #include "dqp_dyn_models.h"   // row_sum (DPP row reduction)
+#include "dqp_al_bounds.h"
 
 #ifdef DQP_STAMPS
 namespace dqp { extern unsigned long long *g_debug_stamps; }
 #endif
 
 namespace {
+
+using dqp::StridedBounds;
+using dqp::strided_bounds;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -497,8 +503,13 @@ struct MeritP {
     double *merit;
     int B, n, m, T, ncand;
 };
+// the argument of the strided kernel: + the bound layout (dqp_al_bounds.h).  The vector kernels keep their argument
+// struct, so that not even the offsets of their hidden kernel arguments move.
+struct MeritPS : MeritP { long long bsb, bst; };
+template <bool SB> using MeritArg = std::conditional_t<SB, MeritPS, MeritP>;
 
-__global__ __launch_bounds__(256) void al_merit_kernel(MeritP P)
+// SB: per-sample / per-knot bounds at [b bsb + t bst + i]; !SB: the n_ctrl-vector
+template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritArg<SB> P)
 {
     const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, ncon = neq + 2 * T * m;
     const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // (cand, problem)
@@ -522,7 +533,10 @@ __global__ __launch_bounds__(256) void al_merit_kernel(MeritP P)
             acc += (0.5 * rho * res + lam[row]) * res;
         }
         for (int i = 0; i < m; ++i) {                       // box rows of knot t
-            const double u = z[n + i], up = u - P.uu[i], lo = P.ul[i] - u;
+            double uut, ult;
+            if constexpr (SB) { uut = P.uu[b * P.bsb + t * P.bst + i]; ult = P.ul[b * P.bsb + t * P.bst + i]; }
+            else { uut = P.uu[i]; ult = P.ul[i]; }
+            const double u = z[n + i], up = u - uut, lo = ult - u;
             const int row = neq + t * 2 * m + i;
             acc += lam[row] * up + lam[row + m] * lo + 0.5 * rho * (fmax(up, 0.0) * fmax(up, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
         }
@@ -575,10 +589,12 @@ struct LinP {
     double dt;
     int B, n, m, T, dyn;
 };
+struct LinPS : LinP { long long bsb, bst; };        // + the bound layout, for the strided kernel
+template <bool SB> using LinArg = std::conditional_t<SB, LinPS, LinP>;
 
 // one thread per (problem, knot): dynamics + Jacobians of the knot, its equality rows
 // x_{t+1} - f(x_t, u_t) (or x_0 - x0 for the last block) and its clamped box rows
-__global__ __launch_bounds__(256) void al_linearize_kernel(LinP P)
+template <bool SB> __global__ __launch_bounds__(256) void al_linearize_kernel(LinArg<SB> P)
 {
     const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, ncon = neq + 2 * T * m;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -607,8 +623,13 @@ __global__ __launch_bounds__(256) void al_linearize_kernel(LinP P)
     }
     for (int i = 0; i < m; ++i) {
         const double u = z[n + i];
-        resc[neq + t * 2 * m + i] = fmax(u - P.uu[i], 0.0);
-        resc[neq + t * 2 * m + m + i] = fmax(P.ul[i] - u, 0.0);
+        if constexpr (SB) {
+            resc[neq + t * 2 * m + i] = fmax(u - P.uu[b * P.bsb + t * P.bst + i], 0.0);
+            resc[neq + t * 2 * m + m + i] = fmax(P.ul[b * P.bsb + t * P.bst + i] - u, 0.0);
+        } else {
+            resc[neq + t * 2 * m + i] = fmax(u - P.uu[i], 0.0);
+            resc[neq + t * 2 * m + m + i] = fmax(P.ul[i] - u, 0.0);
+        }
     }
 }
 
@@ -623,6 +644,10 @@ struct LsAP {
     int32_t *fail;
     const int32_t *info;
 };
+// + the bound layout (dqp_al_bounds.h): the argument of the StridedBounds<> instantiations, and what the host code
+// carries; a vector instantiation is launched with the LsAP part of it
+struct LsAPS : LsAP { long long bsb, bst; };
+template <class Map> using LsArg = std::conditional_t<strided_bounds<Map>::value, LsAPS, LsAP>;
 
 // merit (al_utils.py:37-59) of ncand candidates xu + 2^-k upd per problem (x_0 pinned to x0,
 // al_utils.py:515), dynamics evaluated in the kernel; 16 lanes per (candidate, problem).  ncand = 0
@@ -632,7 +657,7 @@ struct LsAP {
 //   phase B  one knot per lane: the model step from the knot in LDS (odd stride: conflict-free),
 //            residual against the next knot in LDS, multiplier and penalty terms
 template <class Map>
-__global__ __launch_bounds__(256) void al_ls_kernel(LsAP P)
+__global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     __shared__ double ls_lds[16 * 17 * ZS];
@@ -649,6 +674,7 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsAP P)
     const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
     const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
     const double rho = P.rho[b];
+    constexpr bool SB = strided_bounds<Map>::value;
     double *zb = ls_lds + slot * 17 * ZS;
     double acc = 0.0;
     for (int c = 0; c < T; c += 16) {
@@ -663,7 +689,10 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsAP P)
                 acc += (0.5 * Qd[ge] * z + q[ge]) * z;
                 if (j >= n) {
                     const int i = j - n, row = neq + t * 2 * m + i;
-                    const double hi = z - P.uu[i], lo = P.ul[i] - z;
+                    double uut, ult;
+                    if constexpr (SB) { uut = P.uu[b * P.bsb + t * P.bst + i]; ult = P.ul[b * P.bsb + t * P.bst + i]; }
+                    else { uut = P.uu[i]; ult = P.ul[i]; }
+                    const double hi = z - uut, lo = ult - z;
                     acc += lam[row] * hi + lam[row + m] * lo +
                            0.5 * rho * (fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
                 }
@@ -726,7 +755,7 @@ __device__ __forceinline__ void group_sync()
 }
 
 template <class Map, int TPI, int TMAX>
-__global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12) ? 2 : 1) void al_ls_group_kernel(LsAP P)
+__global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12) ? 2 : 1) void al_ls_group_kernel(LsArg<Map> P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     constexpr int EPL = (TMAX * nt + TPI - 1) / TPI;       // elements of the (T, nt) arrays per lane, T <= TMAX
@@ -777,7 +806,12 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
         const int ec = t * nt + n + iu, row = neq + t * 2 * m + iu;
         cx[i] = ok ? xu[ec] : 0.0; cu[i] = (ok && P.ncand > 0) ? up[ec] : 0.0;
         lu[i] = ok ? lam[row] : 0.0; ll[i] = ok ? lam[row + m] : 0.0;
-        hi[i] = ok ? P.uu[iu] : INFINITY; lo[i] = ok ? P.ul[iu] : -INFINITY;
+        if constexpr (strided_bounds<Map>::value) {       // the element's own knot: once, with its multipliers
+            const long long bo = b * P.bsb + t * P.bst + iu;
+            hi[i] = ok ? P.uu[bo] : INFINITY; lo[i] = ok ? P.ul[bo] : -INFINITY;
+        } else {
+            hi[i] = ok ? P.uu[iu] : INFINITY; lo[i] = ok ? P.ul[iu] : -INFINITY;
+        }
     }
     // multipliers of the lane's dynamics rows: registers, or -- long knots -- the group's LDS rows behind its iterate
     double ly[POLY ? 1 : n];
@@ -856,7 +890,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     }
 }
 
-template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAP &P, hipStream_t st)
+template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPS &P, hipStream_t st)
 {
     constexpr int ZS = (Map::NX + Map::NU) | 1, G = 256 / TPI;
     constexpr bool POLY = (TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12;
@@ -865,11 +899,11 @@ template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAP &P,
     // at least ~2 wavefronts per SIMD where the batch alone does not give them: split the candidates
     unsigned split = 1;
     if (P.ncand > 1) while (split < 4 && (unsigned long long)blocks * 4 * split < 2048) split *= 2;
-    DQP_LAUNCH((al_ls_group_kernel<Map, TPI, TMAX>), dim3(blocks, split), dim3(256), lds, st, P);
+    DQP_LAUNCH((al_ls_group_kernel<Map, TPI, TMAX>), dim3(blocks, split), dim3(256), lds, st, static_cast<const LsArg<Map> &>(P));
     return (P.xu_w && split == 1 && P.ncand > 0) ? 2 : DQP_OK;     // 2: the selection happened in the kernel
 }
 
-template <class Map> int launch_ls_t(const LsAP &P, hipStream_t st)
+template <class Map> int launch_ls_t(const LsAPS &P, hipStream_t st)
 {
     // the model phase keeps T - 1 lanes of a group busy: four lanes for the shortest horizons (config 5: T = 5)
     if (P.T <= 5) return launch_ls_group<Map, 4, 5>(P, st);
@@ -877,20 +911,25 @@ template <class Map> int launch_ls_t(const LsAP &P, hipStream_t st)
     if (P.T <= 16) return launch_ls_group<Map, 16>(P, st);
     if (P.T <= 32) return launch_ls_group<Map, 32>(P, st);
     const long long items = (long long)(P.ncand > 0 ? P.ncand : 1) * P.B;
-    DQP_LAUNCH(al_ls_kernel<Map>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, P);
+    DQP_LAUNCH(al_ls_kernel<Map>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, static_cast<const LsArg<Map> &>(P));
     return DQP_OK;
 }
 
-int launch_ls(const LsAP &P, hipStream_t st)
+template <class Model> int launch_ls_layout(const LsAPS &P, hipStream_t st)
+{
+    return (P.bsb != 0 || P.bst != 0) ? launch_ls_t<StridedBounds<Model>>(P, st) : launch_ls_t<Model>(P, st);
+}
+
+int launch_ls(const LsAPS &P, hipStream_t st)
 {
     switch (P.dyn) {
-    case DQP_DYN_PENDULUM1L: return launch_ls_t<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>(P, st);
-    case DQP_DYN_CARTPOLE1L: return launch_ls_t<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>(P, st);
-    case DQP_DYN_CARTPOLE2L: return launch_ls_t<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>(P, st);
-    case DQP_DYN_PENDULUM_EULER: return launch_ls_t<dqp::dyn::PendulumEuler>(P, st);
-    case DQP_DYN_PENDULUM_DX: return launch_ls_t<dqp::dyn::PendulumDx>(P, st);
-    case DQP_DYN_REXQUADROTOR: return launch_ls_t<dqp::dyn::RexQuadrotor>(P, st);
-    case DQP_DYN_INTEGRATOR: return launch_ls_t<dqp::dyn::Integrator>(P, st);
+    case DQP_DYN_PENDULUM1L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>(P, st);
+    case DQP_DYN_CARTPOLE1L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>(P, st);
+    case DQP_DYN_CARTPOLE2L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>(P, st);
+    case DQP_DYN_PENDULUM_EULER: return launch_ls_layout<dqp::dyn::PendulumEuler>(P, st);
+    case DQP_DYN_PENDULUM_DX: return launch_ls_layout<dqp::dyn::PendulumDx>(P, st);
+    case DQP_DYN_REXQUADROTOR: return launch_ls_layout<dqp::dyn::RexQuadrotor>(P, st);
+    case DQP_DYN_INTEGRATOR: return launch_ls_layout<dqp::dyn::Integrator>(P, st);
     default: return DQP_ERR_BAD_ARG;
     }
 }
@@ -901,6 +940,7 @@ struct OutP {
     double dt;
     int B, n, m, T, dyn;
     double *rho_next;       // optional: rho * 10 (AL_mpc.py:307), for the next AL iteration of dqp_al_mpc_solve
+    long long bsb, bst;     // bound layout (dqp_al_bounds.h), read by the StridedBounds<> instantiations only
 };
 
 // Between two AL iterations (qpth/AL_mpc.py:296-307): res = constraint residual at the new iterate,
@@ -919,6 +959,7 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
     const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
     double *ln = P.lam_new + b * (long long)ncon;
     const double rho = P.rho[b];
+    constexpr bool SB = strided_bounds<Map>::value;
     double cost = 0.0, rn2 = 0.0;
     for (int t = r; t < T; t += 16) {
         double z[nt], xn[n];
@@ -940,7 +981,10 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
             }
         }
         for (int i = 0; i < m; ++i) {
-            const double u = z[n + i], hi = u - P.uu[i], lo = P.ul[i] - u;
+            double uut, ult;
+            if constexpr (SB) { uut = P.uu[b * P.bsb + t * P.bst + i]; ult = P.ul[b * P.bsb + t * P.bst + i]; }
+            else { uut = P.uu[i]; ult = P.ul[i]; }
+            const double u = z[n + i], hi = u - uut, lo = ult - u;
             const int row = neq + t * 2 * m + i;
             rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
             if (live) {
@@ -1009,6 +1053,19 @@ __global__ __launch_bounds__(256) void al_start_kernel(StartP P)
 int launch_outer(const OutP &P, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.B + 15) / 16)), block(256);
+    if (P.bsb != 0 || P.bst != 0) {
+        switch (P.dyn) {
+        case DQP_DYN_PENDULUM1L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>>, grid, block, 0, st, P); break;
+        case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>>, grid, block, 0, st, P); break;
+        case DQP_DYN_CARTPOLE2L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>>, grid, block, 0, st, P); break;
+        case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::PendulumEuler>>, grid, block, 0, st, P); break;
+        case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::PendulumDx>>, grid, block, 0, st, P); break;
+        case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::RexQuadrotor>>, grid, block, 0, st, P); break;
+        case DQP_DYN_INTEGRATOR: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Integrator>>, grid, block, 0, st, P); break;
+        default: return DQP_ERR_BAD_ARG;
+        }
+        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    }
     switch (P.dyn) {
     case DQP_DYN_PENDULUM1L: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>, grid, block, 0, st, P); break;
     case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>, grid, block, 0, st, P); break;
@@ -1126,19 +1183,33 @@ dqp_al_assemble(const dqp_al_mpc_dims *d, const double *Jx, const double *Ju, co
 }
 
 __attribute__((visibility("default"))) int
+dqp_al_merit_bounds(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, const double *x_next,
+                    const double *x0, const double *Qdiag, const double *q, const double *lam,
+                    const double *rho, const dqp_al_bounds *bounds, double *merit, void *stream)
+{
+    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || ncand < 0) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    if (d->nbatch == 0 || ncand == 0) return DQP_OK;
+    if (!xu || !x_next || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !merit)
+        return DQP_ERR_BAD_ARG;
+    MeritPS P = {{xu, x_next, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, merit, d->nbatch, d->n_state,
+                 d->n_ctrl, d->T, ncand}, (long long)bounds->stride_b, (long long)bounds->stride_t};
+    const long long total = (long long)ncand * d->nbatch;
+    if (dqp::al_bounds_strided(bounds))
+        DQP_LAUNCH(al_merit_kernel<true>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream, P);
+    else
+        DQP_LAUNCH(al_merit_kernel<false>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
+                   static_cast<const MeritP &>(P));
+    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+}
+
+__attribute__((visibility("default"))) int
 dqp_al_merit(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, const double *x_next,
              const double *x0, const double *Qdiag, const double *q, const double *lam,
              const double *rho, const double *u_lower, const double *u_upper, double *merit, void *stream)
 {
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || ncand < 0) return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0 || ncand == 0) return DQP_OK;
-    if (!xu || !x_next || !x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !merit)
-        return DQP_ERR_BAD_ARG;
-    MeritP P = {xu, x_next, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, d->nbatch, d->n_state,
-                d->n_ctrl, d->T, ncand};
-    const long long total = (long long)ncand * d->nbatch;
-    DQP_LAUNCH(al_merit_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_merit_bounds(d, ncand, xu, x_next, x0, Qdiag, q, lam, rho, &bd, merit, stream);
 }
 
 
@@ -1159,8 +1230,18 @@ __attribute__((visibility("default"))) size_t dqp_al_newton_solve_bytes(const dq
 
 static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
                              const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
-                             const double *u_lower, const double *u_upper, double *xu, double *L, double *status,
+                             const dqp_al_bounds *bounds, double *xu, double *L, double *status,
                              int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor = true);
+
+__attribute__((visibility("default"))) int
+dqp_al_newton_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
+                           const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
+                           const dqp_al_bounds *bounds, double *xu, double *L, double *status,
+                           int32_t *fail, void *workspace, void *stream)
+{
+    return newton_solve_impl(d, dyn_id, dt, n_steps, banded, x0, Qdiag, q, lam, rho, bounds, xu, L, status, fail,
+                             workspace, stream, true);
+}
 
 __attribute__((visibility("default"))) int
 dqp_al_newton_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
@@ -1168,20 +1249,24 @@ dqp_al_newton_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_s
                     const double *u_lower, const double *u_upper, double *xu, double *L, double *status,
                     int32_t *fail, void *workspace, void *stream)
 {
-    return newton_solve_impl(d, dyn_id, dt, n_steps, banded, x0, Qdiag, q, lam, rho, u_lower, u_upper, xu, L, status, fail,
-                             workspace, stream, true);
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_newton_solve_bounds(d, dyn_id, dt, n_steps, banded, x0, Qdiag, q, lam, rho, &bd, xu, L, status, fail,
+                                      workspace, stream);
 }
 
 // clear_fail = false: the caller's own kernel zeroed the flag (dqp_al_mpc_solve: al_start_kernel clears all of them)
 static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
                              const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
-                             const double *u_lower, const double *u_upper, double *xu, double *L, double *status,
+                             const dqp_al_bounds *bounds, double *xu, double *L, double *status,
                              int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor)
 {
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || n_steps < 1) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
     int32_t dn = 0, dm = 0;
     if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
+    const long long bsb = bounds->stride_b, bst = bounds->stride_t;
     if (!x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !xu || !fail || !workspace) return DQP_ERR_BAD_ARG;
     const int B = d->nbatch, n = d->n_state, m = d->n_ctrl, T = d->T, nt = n + m, nz = T * nt;
     const int ncon = T * n + 2 * T * m;
@@ -1197,16 +1282,16 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
         double *merit_cur = w;     w += (size_t)B;
         int32_t *info = (int32_t *)w;
         if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-        LsAP Lp = {xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id};
+        LsAPS Lp = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst};
         int rc0 = launch_ls(Lp, st);                                    // merit at the start
         if (rc0) return rc0;
         for (int it = 0; it < n_steps; ++it) {
             // only the last step's factor is used afterwards (NewtonAL.backward, al_utils.py:477-480)
-            int rc = dqp::al_banded_newton_step_keep(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, u_lower, u_upper, upd, L,
-                                                     info, stream, (it == n_steps - 1 && keep_factor) ? 1 : 0);
+            int rc = dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, upd, L, info,
+                                                            stream, (it == n_steps - 1 && keep_factor) ? 1 : 0);
             if (rc) return rc;
-            LsAP Lc = {xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id,
-                       xu, merit_cur, status, fail, info};
+            LsAPS Lc = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id,
+                         xu, merit_cur, status, fail, info}, bsb, bst};
             rc = launch_ls(Lc, st);
             if (rc != DQP_OK && rc != 2) return rc;
             if (rc != 2) {          // candidates split over several groups: select in a launch of its own
@@ -1232,12 +1317,16 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
     double *merit_cur = w;     w += (size_t)B;
     int32_t *info = (int32_t *)w;
     if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-    LsAP Lp = {xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id};
+    LsAPS Lp = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst};
     rc = launch_ls(Lp, st);                                             // merit at the start
     if (rc) return rc;
     for (int it = 0; it < n_steps; ++it) {
-        LinP Li = {xu, x0, u_lower, u_upper, Jx, Ju, resc, dt, B, n, m, T, dyn_id};
-        DQP_LAUNCH(al_linearize_kernel, dim3((unsigned)(((long long)B * T + 255) / 256)), dim3(256), 0, st, Li);
+        LinPS Li = {{xu, x0, u_lower, u_upper, Jx, Ju, resc, dt, B, n, m, T, dyn_id}, bsb, bst};
+        if (bsb != 0 || bst != 0)       // the clamped box rows carry the layout; the dense assembly and factorisation read them
+            DQP_LAUNCH(al_linearize_kernel<true>, dim3((unsigned)(((long long)B * T + 255) / 256)), dim3(256), 0, st, Li);
+        else
+            DQP_LAUNCH(al_linearize_kernel<false>, dim3((unsigned)(((long long)B * T + 255) / 256)), dim3(256), 0, st,
+                       static_cast<const LinP &>(Li));
         AsmP As = {Jx, Ju, lam, resc, rho, Jc, grad, B, n, m, T, Qdiag, q, xu};
         DQP_LAUNCH(al_assemble_kernel, dim3(B), dim3(256), 0, st, As);
         AlP P = A;
@@ -1253,7 +1342,7 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
         default: rc = launch(al_newton_kernel<8>, P, lds, stream); break;
         }
         if (rc) return rc;
-        LsAP Lc = {xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id};
+        LsAPS Lc = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id}, bsb, bst};
         rc = launch_ls(Lc, st);
         if (rc) return rc;
         SelP Se = {merit, upd, x0, xu, merit_cur, status, fail, info, B, n, nz, 20};
@@ -1269,7 +1358,18 @@ dqp_al_outer_update(const dqp_al_mpc_dims *d, int dyn_id, double dt, const doubl
                     const double *u_lower, const double *u_upper, double *lam_new, double *cost,
                     double *res_norm, void *stream)
 {
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_outer_update_bounds(d, dyn_id, dt, xu, x0, lam, rho, Qdiag, q, &bd, lam_new, cost, res_norm, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
+                           const double *lam, const double *rho, const double *Qdiag, const double *q,
+                           const dqp_al_bounds *bounds, double *lam_new, double *cost, double *res_norm, void *stream)
+{
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (d->nbatch == 0) return DQP_OK;
     int32_t dn = 0, dm = 0;
     if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
@@ -1277,7 +1377,7 @@ dqp_al_outer_update(const dqp_al_mpc_dims *d, int dyn_id, double dt, const doubl
     if (!xu || !x0 || !lam || !rho || !Qdiag || !q || !u_lower || !u_upper || !lam_new || !cost || !res_norm)
         return DQP_ERR_BAD_ARG;
     OutP P = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, lam_new, cost, res_norm, dt, d->nbatch, d->n_state,
-              d->n_ctrl, d->T, dyn_id, nullptr};
+              d->n_ctrl, d->T, dyn_id, nullptr, (long long)bounds->stride_b, (long long)bounds->stride_t};
     return launch_outer(P, (hipStream_t)stream);
 }
 
@@ -1294,9 +1394,25 @@ dqp_al_mpc_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_ite
                  double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
                  double *status, int32_t *fail, void *workspace, void *stream)
 {
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_mpc_solve_bounds(d, dyn_id, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, &bd, lam_in, rho_in,
+                                   prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho, res_norm, factor,
+                                   status, fail, workspace, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                        const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
+                        const dqp_al_bounds *bounds, const double *lam_in, const double *rho_in,
+                        const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                        double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
+                        double *status, int32_t *fail, void *workspace, void *stream)
+{
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
         n_prev < 0)
         return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (d->nbatch == 0) return DQP_OK;
     if (!x_init || !u_init || !x0 || !Qdiag || !q || !u_lower || !u_upper || !lam_in || !rho_in || !xu || !hist_cost ||
         !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
@@ -1311,11 +1427,12 @@ dqp_al_mpc_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_ite
     DQP_LAUNCH(al_start_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
     for (int i = 0; i < al_iter; ++i) {
         const double *lam = hist_lam + (long long)i * B * ncon, *rho = hist_rho + (long long)i * B;
-        int rc = newton_solve_impl(d, dyn_id, dt, newton_steps, 1, x0, Qdiag, q, lam, rho, u_lower, u_upper, xu, factor,
+        int rc = newton_solve_impl(d, dyn_id, dt, newton_steps, 1, x0, Qdiag, q, lam, rho, bounds, xu, factor,
                                    status, fail + i, workspace, stream, false, i == al_iter - 1);
         if (rc) return rc;
         OutP O = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, hist_lam + (long long)(i + 1) * B * ncon,
-                  hist_cost + (long long)(i + 1) * B, res_norm, dt, B, n, m, T, dyn_id, hist_rho + (long long)(i + 1) * B};
+                  hist_cost + (long long)(i + 1) * B, res_norm, dt, B, n, m, T, dyn_id, hist_rho + (long long)(i + 1) * B,
+                  (long long)bounds->stride_b, (long long)bounds->stride_t};
         if ((rc = launch_outer(O, st)) != DQP_OK) return rc;
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;

@@ -41,10 +41,13 @@
 #include "../../include/dqp.h"
 #include "dqp_r16_prims.h"
 #include "dqp_dyn_models.h"
+#include "dqp_al_bounds.h"
 
 namespace {
 
 using namespace dqp::r16;
+using dqp::StridedBounds;
+using dqp::strided_bounds;
 using dqp::dyn::Dual;
 
 struct BandP {
@@ -59,6 +62,8 @@ struct BandP {
     int B, T;
     int keep;           // 0: the caller does not need this step's factor (an intermediate Newton step) -- kernels that hold the
                         // factor on chip (LF below) then leave `fac` untouched; 1: write it
+    long long bsb, bst; // bound layout (dqp_al_bounds.h): ul / uu of (b, t, k) at [b bsb + t bst + k]; read by the
+                        // StridedBounds<> instantiations only, (0, 0) launches the vector ones
 #ifdef DQP_BAND_STAMPS
     unsigned long long *stamps;     // instrumented build (tools/stamps_band.py): 8 accumulated s_memtime phases per workgroup
 #endif
@@ -89,6 +94,7 @@ static unsigned long long *g_band_stamps = nullptr;
 template <int NX_, int NU_> struct Given { static constexpr int NX = NX_, NU = NU_; };
 template <class M> struct is_given { static constexpr bool value = false; };
 template <int A, int B_> struct is_given<Given<A, B_>> { static constexpr bool value = true; };
+template <class M> struct is_given<StridedBounds<M>> : is_given<M> {};
 
 template <class Map> struct BandCfg {
     static constexpr int NX = Map::NX, NU = Map::NU, NT = NX + NU;
@@ -258,6 +264,10 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
     const double rho = P.rho[b];
     double *fac = P.fac + b * (long long)T * NT * C::ROW;
     const bool inT = r < NT;
+    // per-sample / per-knot bounds: the sample's rows; a knot's pair is loaded once per knot, with its multipliers
+    constexpr bool SB = strided_bounds<Map>::value;
+    const double *ulb = P.ul, *uub = P.uu;
+    if constexpr (SB) { ulb += b * P.bsb; uub += b * P.bsb; }
 
     double Mprev[NX], yprev[1] = {0.0}, mu_prev[NX];
     int bad = 0;
@@ -346,7 +356,10 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
                 for (int j = 0; j < NX; ++j) prev = (r == j) ? mu_prev[j] : prev;
                 const double first = lam[(T - 1) * NX + rx] + rho * (zr - x0[rx]);
                 const int row = neq + t * 2 * NU + i;
-                const double rup = zr - P.uu[i], rlo = P.ul[i] - zr;
+                double uut, ult;
+                if constexpr (SB) { uut = uub[t * P.bst + i]; ult = ulb[t * P.bst + i]; }
+                else { uut = P.uu[i]; ult = P.ul[i]; }
+                const double rup = zr - uut, rlo = ult - zr;
                 const double lup = lam[row], llo = lam[row + NU];
                 if (r < NX) {
                     g += (t > 0) ? prev : first;
@@ -429,7 +442,8 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
         // computes and write knot t's factor rows while knot t + 1 computes: a knot was one exposed memory round trip
         // in front of ~2.5 k instructions, and its stores were in the way of the next knot's loads (vmcnt is in order).
         const int rr = inT ? r : 0, rx = r < NX ? r : 0, iu = (inT && r >= NX) ? r - NX : 0;
-        const double x0r = x0[rx], lam_first = lam[(T - 1) * NX + rx], uur = P.uu[iu], ulr = P.ul[iu];       // knot-independent
+        const double x0r = x0[rx], lam_first = lam[(T - 1) * NX + rx];                                        // knot-independent
+        const double uur = SB ? 0.0 : P.uu[iu], ulr = SB ? 0.0 : P.ul[iu];        // the vector bounds are, too
         // KB ("knot batching"): a group of G lanes has G / nt times the lanes one knot's nt forward-mode seeds need -- three
         // knots' worth at cartpole-1 on a 16-lane row, five at the pendulums -- and the model evaluation is the larger part
         // of a knot (1.1 k of 1.8 k instructions at cartpole-1).  Every KP knots the lanes evaluate the model of KP knots at
@@ -450,7 +464,7 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
     #pragma unroll
             for (int j = 0; j < NX; ++j) pxnk[j] = xu[tn * NT + j];
         };
-        double pz[NT], pxn1[NX], plam[NX], pfx[NX], pcol[NX], pzr, pqd, pq, plu, pll;
+        double pz[NT], pxn1[NX], plam[NX], pfx[NX], pcol[NX], pzr, pqd, pq, plu, pll, puu = 0.0, pul = 0.0;
         auto load_knot = [&](int t) {
             const bool dynrow = t < T - 1;
             if constexpr (!KB) {
@@ -476,6 +490,7 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
             pzr = xu[t * NT + rr]; pqd = Qd[t * NT + rr]; pq = q[t * NT + rr];
             const int row = neq + t * 2 * NU + iu;
             plu = lam[row]; pll = lam[row + NU];
+            if constexpr (SB) { puu = uub[t * P.bst + iu]; pul = ulb[t * P.bst + iu]; }
         };
         double sH[NT], sM[NX], srd = 0.0, sy = 0.0;              // knot t - 1's factor rows, stored during knot t
         auto store_knot = [&](int t, const double (&Hrow)[NT], double rdv, const double (&Mrow)[NX], double yv) {
@@ -506,6 +521,7 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
     #pragma unroll
             for (int j = 0; j < NX; ++j) { lamt[j] = plam[j]; fxv[j] = pfx[j]; colv[j] = pcol[j]; }
             const double zr = pzr, qdr = pqd, qr = pq, lup = plu, llo = pll;
+            const double uut = SB ? puu : uur, ult = SB ? pul : ulr;
             const bool dynrow = t < T - 1;
             if (t + 1 < T) load_knot(t + 1);
             if constexpr (!LF) { if (t > 0) store_knot(t - 1, sH, srd, sM, sy); }
@@ -568,7 +584,7 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P)
     #pragma unroll
                 for (int j = 0; j < NX; ++j) prev = (r == j) ? mu_prev[j] : prev;
                 const double first = lam_first + rho * (zr - x0r);
-                const double rup = zr - uur, rlo = ulr - zr;
+                const double rup = zr - uut, rlo = ult - zr;
                 if (r < NX) {
                     g += (t > 0) ? prev : first;
                     dg += rho;
@@ -858,6 +874,11 @@ template <class Map> int run_newton(const BandP &P_, void *stream)
     DQP_LAUNCH((al_banded_newton_kernel<Map, 16>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
+// the vector instantiation at (0, 0), the strided one otherwise
+template <class Map> int run_newton_layout(const BandP &P, void *stream)
+{
+    return (P.bsb != 0 || P.bst != 0) ? run_newton<StridedBounds<Map>>(P, stream) : run_newton<Map>(P, stream);
+}
 template <class Map> int run_solve(const BandP &P, void *stream)
 {
     if constexpr (half_row<Map>()) {
@@ -933,27 +954,39 @@ __attribute__((visibility("default"))) size_t dqp_al_banded_jac_factor_bytes(con
 
 // dqp_al_banded_newton_step with the caller saying whether it needs this step's factor afterwards (the Newton loop of
 // dqp_al.hip keeps the last step's only)
+int dqp::al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
+                                           const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                           const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info,
+                                           void *stream, int keep)
+{
+    if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
+    int32_t n = 0, m = 0;
+    if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    if (d->nbatch == 0) return DQP_OK;
+    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !update || !factor)
+        return DQP_ERR_BAD_ARG;
+    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, nullptr, nullptr, nullptr, update,
+               (double *)factor, info, dt, d->nbatch, d->T, keep, (long long)bounds->stride_b, (long long)bounds->stride_t};
+    switch (dyn_id) {
+    case DQP_DYN_PENDULUM1L: return run_newton_layout<Robot<Pendulum1l>>(P, stream);
+    case DQP_DYN_CARTPOLE1L: return run_newton_layout<Robot<Cartpole1l>>(P, stream);
+    case DQP_DYN_CARTPOLE2L: return run_newton_layout<Robot<Cartpole2l>>(P, stream);
+    case DQP_DYN_PENDULUM_EULER: return run_newton_layout<PendulumEuler>(P, stream);
+    case DQP_DYN_REXQUADROTOR: return run_newton_layout<RexQuadrotor>(P, stream);
+    case DQP_DYN_INTEGRATOR: return run_newton_layout<Integrator>(P, stream);
+    default: return run_newton_layout<PendulumDx>(P, stream);
+    }
+}
+
 int dqp::al_banded_newton_step_keep(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
                                     const double *Qdiag, const double *q, const double *lam, const double *rho,
                                     const double *u_lower, const double *u_upper, double *update, void *factor,
                                     int32_t *info, void *stream, int keep)
 {
-    if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    int32_t n = 0, m = 0;
-    if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !update || !factor) return DQP_ERR_BAD_ARG;
-    BandP P = {xu, x0, Qdiag, q, lam, rho, u_lower, u_upper, nullptr, nullptr, nullptr, nullptr, update, (double *)factor,
-               info, dt, d->nbatch, d->T, keep};
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return run_newton<Robot<Pendulum1l>>(P, stream);
-    case DQP_DYN_CARTPOLE1L: return run_newton<Robot<Cartpole1l>>(P, stream);
-    case DQP_DYN_CARTPOLE2L: return run_newton<Robot<Cartpole2l>>(P, stream);
-    case DQP_DYN_PENDULUM_EULER: return run_newton<PendulumEuler>(P, stream);
-    case DQP_DYN_REXQUADROTOR: return run_newton<RexQuadrotor>(P, stream);
-    case DQP_DYN_INTEGRATOR: return run_newton<Integrator>(P, stream);
-    default: return run_newton<PendulumDx>(P, stream);
-    }
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, &bd, update, factor, info, stream,
+                                                  keep);
 }
 
 extern "C" {
@@ -966,6 +999,15 @@ dqp_al_banded_newton_step(const dqp_al_mpc_dims *d, int dyn_id, double dt, const
 {
     return dqp::al_banded_newton_step_keep(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, u_lower, u_upper, update, factor, info,
                                            stream, 1);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_banded_newton_step_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
+                                 const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                 const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info, void *stream)
+{
+    return dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, update, factor, info,
+                                                  stream, 1);
 }
 
 __attribute__((visibility("default"))) int
@@ -1000,22 +1042,37 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
  * The same block-tridiagonal Newton step for a dynamics the CALLER linearised (include/dqp.h).
  */
 __attribute__((visibility("default"))) int
+dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *d, const double *xu, const double *x0, const double *Qdiag,
+                                     const double *q, const double *lam, const double *rho, const dqp_al_bounds *bounds,
+                                     const double *x_next, const double *Jx, const double *Ju, double *update,
+                                     void *factor, int32_t *info, void *stream)
+{
+    if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    if (!given_supported(d->n_state, d->n_ctrl) && !given_wide(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
+    // the wide pairs have the vector instantiation only
+    if (dqp::al_bounds_strided(bounds) && !given_supported(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
+    if (d->nbatch == 0) return DQP_OK;
+    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !x_next || !Jx || !Ju || !update ||
+        !factor)
+        return DQP_ERR_BAD_ARG;
+    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, x_next, Jx, Ju, update, (double *)factor,
+               info, 0.0, d->nbatch, d->T, 1, (long long)bounds->stride_b, (long long)bounds->stride_t};
+#define X(a, b) if (d->n_state == a && d->n_ctrl == b) return run_newton_layout<Given<a, b>>(P, stream);
+    DQP_BAND_SIZES
+#undef X
+    return dqp::al_banded_wide_newton(d->n_state, d->n_ctrl, &P, sizeof(P), stream);
+}
+
+__attribute__((visibility("default"))) int
 dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *d, const double *xu, const double *x0, const double *Qdiag,
                               const double *q, const double *lam, const double *rho, const double *u_lower,
                               const double *u_upper, const double *x_next, const double *Jx, const double *Ju,
                               double *update, void *factor, int32_t *info, void *stream)
 {
-    if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
-    if (!given_supported(d->n_state, d->n_ctrl) && !given_wide(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !x_next || !Jx || !Ju || !update || !factor)
-        return DQP_ERR_BAD_ARG;
-    BandP P = {xu, x0, Qdiag, q, lam, rho, u_lower, u_upper, nullptr, x_next, Jx, Ju, update, (double *)factor, info, 0.0,
-               d->nbatch, d->T, 1};
-#define X(a, b) if (d->n_state == a && d->n_ctrl == b) return run_newton<Given<a, b>>(P, stream);
-    DQP_BAND_SIZES
-#undef X
-    return dqp::al_banded_wide_newton(d->n_state, d->n_ctrl, &P, sizeof(P), stream);
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_banded_newton_step_jac_bounds(d, xu, x0, Qdiag, q, lam, rho, &bd, x_next, Jx, Ju, update, factor, info,
+                                                stream);
 }
 
 __attribute__((visibility("default"))) int dqp_al_lane_group(int width)

@@ -32,6 +32,8 @@
 #define DQP_AL_BANDED_KERNELS_ONLY
 #include "dqp_al_banded.hip"
 
+#include <type_traits>
+
 namespace {
 
 struct FusedP {
@@ -42,6 +44,10 @@ struct FusedP {
     double dt;
     int B, T, al_iter, newton_steps, n_prev;
 };
+// + the bound layout (dqp_al_bounds.h): the argument of the StridedBounds<> instantiations and what the host code carries;
+// the vector instantiations keep FusedP as their argument
+struct FusedPS : FusedP { long long bsb, bst; };
+template <class Map> using FusedArg = std::conditional_t<strided_bounds<Map>::value, FusedPS, FusedP>;
 
 constexpr int FG = 8, FNG = 64 / FG;      // lanes per group, groups per wavefront
 constexpr int NCAND = 20;                 // line-search candidates 2^-k, k = 0 .. 19 (al_utils.py:503-527)
@@ -59,14 +65,16 @@ template <class Map> struct FusedLds {
     static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
     static constexpr int JBK = NX * (NT + 1);         // per knot: NX rows of [J[j][0 .. nt-1], res_j]
     __host__ __device__ static int ncon(int T) { return T * NX + 2 * T * NU; }
+    // StridedBounds<>: + the problem's own bounds, upper (T, nu) then lower (T, nu), staged once at the start
+    static constexpr bool SB = strided_bounds<Map>::value;
     __host__ __device__ static size_t doubles(int T)
     {
-        return (size_t)5 * T * NT + ncon(T) + (size_t)T * JBK + (size_t)T * NT * C::ROW + 32;
+        return (size_t)5 * T * NT + ncon(T) + (size_t)T * JBK + (size_t)T * NT * C::ROW + 32 + (SB ? (size_t)2 * T * NU : 0);
     }
 };
 
 template <class Map>
-__global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
+__global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
 {
     using C = BandCfg<Map>;
     using Gr = Grp<FG>;
@@ -82,6 +90,8 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
     extern __shared__ __attribute__((aligned(16))) double fs[];
     double *s_xu = fs, *s_upd = s_xu + nz, *s_y = s_upd + nz, *s_Qd = s_y + nz, *s_q = s_Qd + nz;
     double *s_lam = s_q + nz, *s_jb = s_lam + ncon, *s_fac = s_jb + T * JBK, *s_merit = s_fac + T * NT * ROW;
+    constexpr bool SB = Lds::SB;
+    [[maybe_unused]] double *s_uu = s_merit + 32, *s_ul = s_uu + T * NU;       // SB only (FusedLds::doubles)
     // the group's tile for the transposed copies of the sweep (element (row, col) at [col TS + row])
     constexpr int TS = FG + 2, PS = FG * TS;
     __shared__ __attribute__((aligned(16))) double trs[FNG * PS];
@@ -94,6 +104,13 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 #pragma unroll
     for (int i = 0; i < NU; ++i) { uuv[i] = P.uu[i]; ulv[i] = P.ul[i]; }
     const double x0r = P.x0[b * NX + rx], uur = P.uu[iu], ulr = P.ul[iu];
+    if constexpr (SB) {         // visible to every lane behind the barrier that closes the start phase
+        for (int e = lane; e < T * NU; e += 64) {
+            const int t = e / NU, i = e - t * NU;
+            s_uu[e] = P.uu[b * P.bsb + t * P.bst + i];
+            s_ul[e] = P.ul[b * P.bsb + t * P.bst + i];
+        }
+    }
 
     // ---- start (al_start_kernel): xu = [x_init | u_init], cost_start, warm start of (lam, rho), history row 0
     double rho;
@@ -149,7 +166,9 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 const int row = neq + t * 2 * NU + i;
-                const double vh = z[NX + i] - uuv[i], vl = ulv[i] - z[NX + i];
+                double vh, vl;
+                if constexpr (SB) { vh = z[NX + i] - s_uu[t * NU + i]; vl = s_ul[t * NU + i] - z[NX + i]; }
+                else { vh = z[NX + i] - uuv[i]; vl = ulv[i] - z[NX + i]; }
                 acc += s_lam[row] * vh + s_lam[row + NU] * vl +
                        0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
             }
@@ -214,7 +233,9 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 #pragma unroll
                     for (int j = 0; j < NX; ++j) prev = (r == j) ? mu_prev[j] : prev;
                     const double first = lam_first + rho * (zr - x0r);
-                    const double rup = zr - uur, rlo = ulr - zr;
+                    double rup, rlo;
+                    if constexpr (SB) { rup = zr - s_uu[t * NU + iu]; rlo = s_ul[t * NU + iu] - zr; }    // once per knot
+                    else { rup = zr - uur; rlo = ulr - zr; }
                     if (r < NX) {
                         g += (t > 0) ? prev : first;
                         dg += rho;
@@ -372,7 +393,10 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
                 }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
-                    const double u = z[NX + i], hi = u - uuv[i], lo = ulv[i] - u;
+                    const double u = z[NX + i];
+                    double hi, lo;
+                    if constexpr (SB) { hi = u - s_uu[t * NU + i]; lo = s_ul[t * NU + i] - u; }
+                    else { hi = u - uuv[i]; lo = ulv[i] - u; }
                     const int row = neq + t * 2 * NU + i;
                     rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
                     const double vu = fmax(s_lam[row] + rho * hi, 0.0), vl = fmax(s_lam[row + NU] + rho * lo, 0.0);   // AL_mpc.py:300-301
@@ -400,34 +424,41 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 constexpr size_t FUSED_STATIC_LDS = (size_t)FNG * FG * (FG + 2) * sizeof(double);
 constexpr size_t FUSED_LDS_LIMIT = 64 * 1024;
 
-template <class Map> size_t fused_lds_bytes(int T) { return FusedLds<Map>::doubles(T) * sizeof(double); }
+// `strided`: the StridedBounds<> instantiation, whose carve also holds the problem's 2 T n_ctrl bounds
+template <class Map> size_t fused_lds_bytes(int T, bool strided)
+{
+    return (strided ? FusedLds<StridedBounds<Map>>::doubles(T) : FusedLds<Map>::doubles(T)) * sizeof(double);
+}
 
-size_t fused_lds(int dyn_id, int T)
+size_t fused_lds(int dyn_id, int T, bool strided = false)
 {
     using namespace dqp::dyn;
     switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return fused_lds_bytes<Robot<Pendulum1l>>(T);
-    case DQP_DYN_CARTPOLE1L: return fused_lds_bytes<Robot<Cartpole1l>>(T);
-    case DQP_DYN_CARTPOLE2L: return fused_lds_bytes<Robot<Cartpole2l>>(T);
-    case DQP_DYN_PENDULUM_EULER: return fused_lds_bytes<PendulumEuler>(T);
-    case DQP_DYN_PENDULUM_DX: return fused_lds_bytes<PendulumDx>(T);
-    case DQP_DYN_INTEGRATOR: return fused_lds_bytes<Integrator>(T);
+    case DQP_DYN_PENDULUM1L: return fused_lds_bytes<Robot<Pendulum1l>>(T, strided);
+    case DQP_DYN_CARTPOLE1L: return fused_lds_bytes<Robot<Cartpole1l>>(T, strided);
+    case DQP_DYN_CARTPOLE2L: return fused_lds_bytes<Robot<Cartpole2l>>(T, strided);
+    case DQP_DYN_PENDULUM_EULER: return fused_lds_bytes<PendulumEuler>(T, strided);
+    case DQP_DYN_PENDULUM_DX: return fused_lds_bytes<PendulumDx>(T, strided);
+    case DQP_DYN_INTEGRATOR: return fused_lds_bytes<Integrator>(T, strided);
     default: return 0;
     }
 }
 
-bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id)
+bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id, bool strided = false)
 {
     if (!d || d->T < 2 || d->T > 32 || d->nbatch < 0) return false;
     int32_t n = 0, m = 0;
     if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl || n + m > FG) return false;
-    const size_t lds = fused_lds(dyn_id, d->T);
+    const size_t lds = fused_lds(dyn_id, d->T, strided);
     return lds > 0 && lds + FUSED_STATIC_LDS <= FUSED_LDS_LIMIT;
 }
 
-template <class Map> int launch_fused(const FusedP &P, size_t lds, hipStream_t st)
+template <class Model> int launch_fused(const FusedPS &P, size_t lds, hipStream_t st)
 {
-    DQP_LAUNCH(al_solve_fused_kernel<Map>, dim3((unsigned)P.B), dim3(64), lds, st, P);
+    if (P.bsb != 0 || P.bst != 0)
+        DQP_LAUNCH(al_solve_fused_kernel<StridedBounds<Model>>, dim3((unsigned)P.B), dim3(64), lds, st, P);
+    else
+        DQP_LAUNCH(al_solve_fused_kernel<Model>, dim3((unsigned)P.B), dim3(64), lds, st, static_cast<const FusedP &>(P));
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
@@ -448,6 +479,30 @@ __attribute__((visibility("default"))) size_t dqp_al_mpc_solve_fused_bytes(const
 }
 
 __attribute__((visibility("default"))) int
+dqp_al_mpc_solve_fused_supported_bounds(const dqp_al_mpc_dims *d, int dyn_id, const dqp_al_bounds *bounds)
+{
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return 0;
+    return fused_ok(d, dyn_id, dqp::al_bounds_strided(bounds)) ? 1 : 0;
+}
+
+// the staged bounds live in LDS (dqp_al_mpc_solve_fused_lds_bytes), not in the workspace: the size of the vector call
+__attribute__((visibility("default"))) size_t
+dqp_al_mpc_solve_fused_bytes_bounds(const dqp_al_mpc_dims *d, const dqp_al_bounds *bounds)
+{
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return 0;
+    return dqp_al_mpc_solve_fused_bytes(d);
+}
+
+// LDS of one workgroup of the launch: the problem's carve (with the 2 T n_ctrl staged bounds at non-zero strides) plus
+// the kernel's static tiles; 0 where dqp_al_mpc_solve_fused_supported_bounds is 0
+__attribute__((visibility("default"))) size_t
+dqp_al_mpc_solve_fused_lds_bytes(const dqp_al_mpc_dims *d, int dyn_id, const dqp_al_bounds *bounds)
+{
+    if (!dqp_al_mpc_solve_fused_supported_bounds(d, dyn_id, bounds)) return 0;
+    return fused_lds(dyn_id, d->T, dqp::al_bounds_strided(bounds)) + FUSED_STATIC_LDS;
+}
+
+__attribute__((visibility("default"))) int
 dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
                        const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
                        const double *u_lower, const double *u_upper, const double *lam_in, const double *rho_in,
@@ -455,10 +510,27 @@ dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t 
                        double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
                        double *status, int32_t *fail, void *workspace, void *stream)
 {
+    const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
+    return dqp_al_mpc_solve_fused_bounds(d, dyn_id, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, &bd, lam_in,
+                                         rho_in, prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho,
+                                         res_norm, factor, status, fail, workspace, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                              const double *x_init, const double *u_init, const double *x0, const double *Qdiag,
+                              const double *q, const dqp_al_bounds *bounds, const double *lam_in, const double *rho_in,
+                              const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                              double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
+                              double *factor, double *status, int32_t *fail, void *workspace, void *stream)
+{
     using namespace dqp::dyn;
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
         n_prev < 0)
         return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
+    const bool strided = dqp::al_bounds_strided(bounds);
     if (d->nbatch == 0) return DQP_OK;
     if (!x_init || !u_init || !x0 || !Qdiag || !q || !u_lower || !u_upper || !lam_in || !rho_in || !xu || !hist_cost ||
         !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
@@ -466,14 +538,14 @@ dqp_al_mpc_solve_fused(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t 
     if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
     int32_t dn = 0, dm = 0;
     if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
-    if (!fused_ok(d, dyn_id)) return DQP_ERR_TOO_LARGE;
+    if (!fused_ok(d, dyn_id, strided)) return DQP_ERR_TOO_LARGE;
     hipStream_t st = (hipStream_t)stream;
     // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
     if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, st) != hipSuccess) return DQP_ERR_LAUNCH;
-    const FusedP P = {x_init, u_init, x0, Qdiag, q, u_lower, u_upper, lam_in, rho_in, prev_cost, prev_lam, prev_rho,
-                      xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, dt, d->nbatch, d->T, al_iter,
-                      newton_steps, n_prev};
-    const size_t lds = fused_lds(dyn_id, d->T);
+    const FusedPS P = {{x_init, u_init, x0, Qdiag, q, u_lower, u_upper, lam_in, rho_in, prev_cost, prev_lam, prev_rho,
+                        xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, dt, d->nbatch, d->T, al_iter,
+                        newton_steps, n_prev}, (long long)bounds->stride_b, (long long)bounds->stride_t};
+    const size_t lds = fused_lds(dyn_id, d->T, strided);
     switch (dyn_id) {
     case DQP_DYN_PENDULUM1L: return launch_fused<Robot<Pendulum1l>>(P, lds, st);
     case DQP_DYN_CARTPOLE1L: return launch_fused<Robot<Cartpole1l>>(P, lds, st);

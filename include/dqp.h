@@ -592,6 +592,77 @@ int dqp_al_banded_newton_step_jac(const dqp_al_mpc_dims *dims, const double *xu,
  * DQP_BAND_WIDE_SIZES pairs always take a 32-lane half-wavefront and ignore it. */
 int dqp_al_lane_group(int width);
 
+/*
+ * Per-sample, per-knot control bounds (additive at 303).  Every entry point above that takes `u_lower` / `u_upper`
+ * reads a vector of n_ctrl doubles shared by the batch and the horizon.  Its `_bounds` twin below takes the bounds as a
+ * dqp_al_bounds instead -- in the position of the (u_lower, u_upper) pair, every other argument unchanged -- and reads
+ *
+ *     lower[b * stride_b + t * stride_t + k],   upper[the same index]
+ *
+ * for sample b, knot t, control k (element strides).  stride_b is 0 or T * n_ctrl, stride_t is 0 or n_ctrl:
+ *
+ *     (0, 0)                 n_ctrl doubles            the vector form -- the twin then launches exactly the kernels
+ *                                                      of the old entry point, which is itself the twin at (0, 0)
+ *     (0, n_ctrl)            (T, n_ctrl)               the same limits for every sample, varying along the horizon
+ *     (n_ctrl, 0)            (B, 1, n_ctrl)            per sample, constant along the horizon: B n_ctrl doubles, packed
+ *     (T n_ctrl, 0)          (B, T, n_ctrl)            the same, read from knot 0 of a full array
+ *     (T n_ctrl, n_ctrl)     (B, T, n_ctrl)            per sample and per knot
+ *
+ * i.e. stride_t is 0 or n_ctrl and stride_b is 0, T n_ctrl or -- only at stride_t == 0 -- n_ctrl, the packed per-sample
+ * form, so that no caller has to expand its bounds along the horizon.  The largest index read is
+ * (nbatch - 1) stride_b + (T - 1) stride_t + n_ctrl - 1.  Any other stride, a null struct or a null lower / upper pointer
+ * returns DQP_ERR_BAD_ARG (struct and strides are checked in front of the nbatch == 0 return, the pointers behind it, as
+ * every other buffer).  Rows of a knot are [u - upper (m), lower - u (m)] as before; lower == upper at a knot freezes
+ * that control there.
+ *
+ * Kernels: the block-tridiagonal Newton step (registered models and the DQP_BAND_SIZES pairs), the line-search / merit,
+ * outer-update and single-launch kernels have a strided instantiation next to the vector one.  The DQP_BAND_WIDE_SIZES
+ * pairs have none: dqp_al_banded_newton_step_jac_bounds returns DQP_ERR_TOO_LARGE for them at non-zero strides.
+ * dqp_al_banded_solve (NewtonAL.backward) does not read the bounds -- the factor already carries the active set -- and
+ * has no twin.  The single-launch solve stages the 2 T n_ctrl bounds of its problem in LDS next to the problem;
+ * dqp_al_mpc_solve_fused_lds_bytes reports the launch's LDS (0 where _supported_bounds is 0).
+ */
+typedef struct dqp_al_bounds {
+    const double *lower, *upper;
+    int64_t stride_b, stride_t;
+} dqp_al_bounds;
+
+int dqp_al_merit_bounds(const dqp_al_mpc_dims *dims, int32_t ncand, const double *xu, const double *x_next,
+                        const double *x0, const double *Qdiag, const double *q, const double *lam,
+                        const double *rho, const dqp_al_bounds *bounds, double *merit, void *stream);
+int dqp_al_newton_solve_bounds(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t n_steps, int32_t banded,
+                               const double *x0, const double *Qdiag, const double *q, const double *lam,
+                               const double *rho, const dqp_al_bounds *bounds, double *xu, double *L,
+                               double *status, int32_t *fail, void *workspace, void *stream);
+int dqp_al_outer_update_bounds(const dqp_al_mpc_dims *dims, int dyn_id, double dt, const double *xu, const double *x0,
+                               const double *lam, const double *rho, const double *Qdiag, const double *q,
+                               const dqp_al_bounds *bounds, double *lam_new, double *cost, double *res_norm,
+                               void *stream);
+int dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                            const double *x_init, const double *u_init, const double *x0, const double *Qdiag,
+                            const double *q, const dqp_al_bounds *bounds, const double *lam_in, const double *rho_in,
+                            const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                            double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
+                            double *factor, double *status, int32_t *fail, void *workspace, void *stream);
+int dqp_al_mpc_solve_fused_supported_bounds(const dqp_al_mpc_dims *dims, int dyn_id, const dqp_al_bounds *bounds);
+size_t dqp_al_mpc_solve_fused_bytes_bounds(const dqp_al_mpc_dims *dims, const dqp_al_bounds *bounds);
+size_t dqp_al_mpc_solve_fused_lds_bytes(const dqp_al_mpc_dims *dims, int dyn_id, const dqp_al_bounds *bounds);
+int dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t al_iter,
+                                  int32_t newton_steps, const double *x_init, const double *u_init, const double *x0,
+                                  const double *Qdiag, const double *q, const dqp_al_bounds *bounds,
+                                  const double *lam_in, const double *rho_in, const double *prev_cost,
+                                  const double *prev_lam, const double *prev_rho, int32_t n_prev, double *xu,
+                                  double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
+                                  double *factor, double *status, int32_t *fail, void *workspace, void *stream);
+int dqp_al_banded_newton_step_bounds(const dqp_al_mpc_dims *dims, int dyn_id, double dt, const double *xu,
+                                     const double *x0, const double *Qdiag, const double *q, const double *lam,
+                                     const double *rho, const dqp_al_bounds *bounds, double *update, void *factor,
+                                     int32_t *info, void *stream);
+int dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *dims, const double *xu, const double *x0,
+                                         const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                         const dqp_al_bounds *bounds, const double *x_next, const double *Jx,
+                                         const double *Ju, double *update, void *factor, int32_t *info, void *stream);
+
 /* ----------------------------------------------------------------- device dynamics registry */
 
 /*
