@@ -59,7 +59,9 @@ SYMBOLS = ("dqp_version", "dqp_error_string", "dqp_workspace_bytes", "dqp_termin
     # the per-sample / per-knot bound layout (dqp_al_bounds): a twin of every entry point that takes control bounds
     s + "_bounds" for s in ("dqp_al_merit", "dqp_al_newton_solve", "dqp_al_outer_update", "dqp_al_mpc_solve",
                             "dqp_al_mpc_solve_fused_supported", "dqp_al_mpc_solve_fused_bytes", "dqp_al_mpc_solve_fused",
-                            "dqp_al_banded_newton_step", "dqp_al_banded_newton_step_jac")) + ("dqp_al_mpc_solve_fused_lds_bytes",)
+                            "dqp_al_banded_newton_step", "dqp_al_banded_newton_step_jac")) + ("dqp_al_mpc_solve_fused_lds_bytes",) + (
+    # the same for the MPC QP entry points (dqp_mpc_bounds = dqp_al_bounds, with the time-major full layout accepted too)
+    "dqp_mpc_assemble_bounds", "dqp_mpc_qp_forward_bounds", "dqp_mpc_qp_forward_stepped_bounds")
 DQP_DYN = {"pendulum1l": 1, "cartpole1l": 2, "cartpole2l": 3, "pendulum_euler": 4, "pendulum_dx": 5,
            "rexquadrotor": 6, "integrator": 7}
 
@@ -213,6 +215,14 @@ def load():
     lib.dqp_al_mpc_solve_fused_bytes_bounds.argtypes = [_mp, _bp]
     lib.dqp_al_mpc_solve_fused_lds_bytes.restype = ctypes.c_size_t
     lib.dqp_al_mpc_solve_fused_lds_bytes.argtypes = [_mp, ctypes.c_int, _bp]
+    _md, _op = ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)
+    lib.dqp_mpc_assemble_bounds.restype = ctypes.c_int
+    lib.dqp_mpc_assemble_bounds.argtypes = [_md] + [_dp] * 5 + [_bp] + [_dp] * 7
+    lib.dqp_mpc_qp_forward_bounds.restype = ctypes.c_int
+    lib.dqp_mpc_qp_forward_bounds.argtypes = [_md, _op] + [_dp] * 5 + [_bp] + [_dp] * 9
+    lib.dqp_mpc_qp_forward_stepped_bounds.restype = ctypes.c_int
+    lib.dqp_mpc_qp_forward_stepped_bounds.argtypes = ([_md, _op] + [_dp] * 5 + [_bp] + [_dp] + [ctypes.c_int32, ctypes.c_int32]
+                                                      + [_dp] * 9)
     lib.dqp_al_lane_group.restype = ctypes.c_int
     lib.dqp_al_lane_group.argtypes = [ctypes.c_int]
     lib.dqp_mpc_qp_stepped_workspace_bytes.restype = ctypes.c_size_t

@@ -73,20 +73,56 @@ def bounds_layout(u_lower, u_upper, n_batch, T, n_ctrl):
     the strides are (0, 0), (0, m), (m, 0), (T m, m).  Raises ValueError for anything else: lower / upper of different
     shapes, a time-major (T, B, n_ctrl) array, scalars.  fp64 contiguous tensors are passed through as they are (no
     copy, nothing allocated -- a captured call keeps its pointers), others are converted once per call."""
-    strides = _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl)
-    d64 = lambda t: t.detach().double().contiguous()
-    if strides == (0, 0):
-        return DeviceBounds(d64(u_lower).reshape(-1), d64(u_upper).reshape(-1), 0, 0)
-    return DeviceBounds(d64(u_lower), d64(u_upper), *strides)
+    return _device_bounds(u_lower, u_upper, _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl))
 
 
-def _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl):
-    """(stride_b, stride_t) of bounds_layout from the shapes alone; ValueError where it has none"""
+def _bound_shape(u_lower, u_upper):
+    """the common shape of a bound pair; ValueError for anything but two tensors of one shape"""
     if not (torch.is_tensor(u_lower) and torch.is_tensor(u_upper)):
         raise ValueError("control bounds must be tensors")
     if u_lower.shape != u_upper.shape:
         raise ValueError("u_lower %s and u_upper %s differ in shape" % (tuple(u_lower.shape), tuple(u_upper.shape)))
-    shp, m = tuple(u_lower.shape), n_ctrl
+    return tuple(u_lower.shape)
+
+
+def _device_bounds(u_lower, u_upper, strides):
+    """DeviceBounds of a pair whose shape has the element strides `strides`: fp64 contiguous tensors as they are"""
+    # the usual case -- a detached fp64 contiguous tensor -- is handed on as the object it is (no torch call per solve)
+    d64 = lambda t: t if (t.dtype is torch.float64 and not t.requires_grad and t.is_contiguous()) else t.detach().double().contiguous()
+    if strides == (0, 0):
+        flat = lambda t: t if t.dim() == 1 else t.reshape(-1)
+        return DeviceBounds(flat(d64(u_lower)), flat(d64(u_upper)), 0, 0)
+    return DeviceBounds(d64(u_lower), d64(u_upper), *strides)
+
+
+def mpc_bounds_layout(u_lower, u_upper, n_batch, T, n_ctrl):
+    """bounds_layout for qp_wrapper.MPC, which is time-major: -> DeviceBounds for bounds of shape (n_ctrl,), (T, n_ctrl),
+    (T, 1, n_ctrl), (1, B, n_ctrl) or (T, B, n_ctrl), with the strides (0, 0), (0, m), (0, m), (m, 0), (m, B m) of
+    include/dqp.h: dqp_mpc_bounds.  Nothing is expanded and fp64 contiguous tensors are passed through without a copy (a
+    captured call keeps its pointers); the bounds are detached.  ValueError for lower / upper of different shapes, a
+    wrong trailing size, and (B, n_ctrl), which cannot be told from (T, n_ctrl).  lower < upper is required of every
+    pair and not checked: the check would be a host synchronisation."""
+    return _device_bounds(u_lower, u_upper, _mpc_bound_strides(u_lower, u_upper, n_batch, T, n_ctrl))
+
+
+def _mpc_bound_strides(u_lower, u_upper, n_batch, T, n_ctrl):
+    shp, m = _bound_shape(u_lower, u_upper), n_ctrl
+    if shp == (m,):
+        return (0, 0)
+    if shp in ((T, m), (T, 1, m)):
+        return (0, m)
+    if shp == (1, n_batch, m):
+        return (m, 0)
+    if shp == (T, n_batch, m):
+        return (m, n_batch * m)
+    raise ValueError("control bounds of shape %s: expected a float, (n_ctrl,), (T, n_ctrl), (T, 1, n_ctrl), (1, B, n_ctrl) or "
+                     "(T, B, n_ctrl) with T = %d, B = %d, n_ctrl = %d (time-major; per-sample bounds are (1, B, n_ctrl), "
+                     "not (B, n_ctrl))" % (shp, T, n_batch, m))
+
+
+def _bound_strides(u_lower, u_upper, n_batch, T, n_ctrl):
+    """(stride_b, stride_t) of bounds_layout from the shapes alone; ValueError where it has none"""
+    shp, m = _bound_shape(u_lower, u_upper), n_ctrl
     if u_lower.numel() == m:            # the vector, in whatever shape holds n_ctrl numbers (as before)
         return (0, 0)
     if shp == (T, m):

@@ -30,6 +30,17 @@ inline int al_bounds_layout(const dqp_al_bounds *b, const dqp_al_mpc_dims *d)
 }
 inline bool al_bounds_strided(const dqp_al_bounds *b) { return b->stride_b != 0 || b->stride_t != 0; }
 
+// The same for the MPC QP entry points (dqp_mpc_bounds of include/dqp.h), which take the time-major full layout too:
+// (0, 0), (0, m), (m, 0), (m, B m), (T m, m).
+inline int mpc_bounds_layout(const dqp_mpc_bounds *b, const dqp_mpc_dims *d)
+{
+    if (!b || !d || d->n_ctrl <= 0 || d->T <= 0 || d->nbatch < 0) return DQP_ERR_BAD_ARG;
+    const int64_t m = d->n_ctrl, Tm = (int64_t)d->T * m, Bm = (int64_t)d->nbatch * m;
+    const int64_t sb = b->stride_b, st = b->stride_t;
+    const bool ok = (sb == 0 && (st == 0 || st == m)) || (sb == m && (st == 0 || st == Bm)) || (sb == Tm && st == m);
+    return ok ? DQP_OK : DQP_ERR_BAD_ARG;
+}
+
 // dqp_al_banded.hip: dqp_al_banded_newton_step_bounds with `keep` = does the caller use this step's factor afterwards
 int al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
                                       const double *Qdiag, const double *q, const double *lam, const double *rho,

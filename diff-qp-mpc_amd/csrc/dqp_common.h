@@ -50,6 +50,18 @@ struct KParams {
     int itBegin, itEnd;
 };
 
+// Layout of the control bounds of an MPC-structured call (include/dqp.h: dqp_mpc_bounds): the pair of sample b, knot t,
+// control k is at mul / muu [b stride_b + t stride_t + k].  The two strides travel in sG and sh, the dense strides that an
+// MPC-structured call never reads (its G and h are built in registers), so the parameter block -- and with it the
+// hidden-argument offsets of every kernel that takes one -- stays as it was.  (0, 0) is the n_ctrl-vector.
+__host__ __device__ inline long long mpc_bound_stride_b(const KParams &P) { return P.sG; }
+__host__ __device__ inline long long mpc_bound_stride_t(const KParams &P) { return P.sh; }
+inline bool mpc_bounds_strided(const KParams &P) { return P.sG != 0 || P.sh != 0; }
+inline void mpc_set_bounds(KParams &P, const dqp_al_bounds *b)
+{
+    P.mul = b->lower; P.muu = b->upper; P.sG = b->stride_b; P.sh = b->stride_t;
+}
+
 constexpr int TERM_HDR = 8;   // int32 header words in front of the per-problem best-iteration list
 
 // Termination buffer (dqp_termination_bytes), see dqp_term.hip: hist [histIters][B] x (resid, mu),

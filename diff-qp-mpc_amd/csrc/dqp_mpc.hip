@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/dqp.h"
+#include "dqp_al_bounds.h"
 #include "dqp_dyn_models.h"
 #include "dqp_trace.h"
 
@@ -96,6 +97,25 @@ __global__ __launch_bounds__(256) void assemble_kernel(MpcP P)
             }
             P.h[e] = v;
         }
+    }
+}
+
+// Bounds per sample and knot (dqp_mpc_assemble_bounds at non-zero strides): h = [u_upper ; -u_lower] with the pair of
+// sample b, knot t, control ju at [b stride_b + t stride_t + ju].  Launched behind assemble_kernel, which has written
+// everything else (and an h from the first n_ctrl bounds, overwritten here): that kernel and its argument block stay
+// exactly as they were.  The layout is an argument of its own.
+struct BoundStrides { long long b, t; };
+__global__ __launch_bounds__(256) void assemble_bounds_kernel(MpcP P, BoundStrides bs)
+{
+    const int m = P.m, T = P.T, nineq = 2 * T * m;
+    const long long nh = (long long)P.B * nineq;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nh; e += (long long)gridDim.x * blockDim.x) {
+        const int row = e % nineq;
+        const long long b = e / nineq;
+        const int k = row < T * m ? row : row - T * m;      // k = t m + ju
+        const int t = k / m, ju = k - t * m;
+        const long long at = b * bs.b + t * bs.t + ju;
+        P.h[e] = row < T * m ? P.uu[at] : -P.ul[at];
     }
 }
 
@@ -433,10 +453,21 @@ dqp_mpc_assemble(const dqp_mpc_dims *d, const double *C, const double *c, const 
                  const double *f, const double *x0, const double *u_lower, const double *u_upper,
                  double *Q, double *p, double *G, double *h, double *A, double *b, void *stream)
 {
+    const dqp_mpc_bounds bounds = {u_lower, u_upper, 0, 0};
+    return dqp_mpc_assemble_bounds(d, C, c, F, f, x0, &bounds, Q, p, G, h, A, b, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_mpc_assemble_bounds(const dqp_mpc_dims *d, const double *C, const double *c, const double *F,
+                        const double *f, const double *x0, const dqp_mpc_bounds *bounds,
+                        double *Q, double *p, double *G, double *h, double *A, double *b, void *stream)
+{
     int rc = check(d);
     if (rc) return rc;
+    if ((rc = dqp::mpc_bounds_layout(bounds, d)) != DQP_OK) return rc;
     if (d->nbatch == 0) return DQP_OK;
     if (!C || !c || !F || !f || !x0 || !Q || !p || !G || !h || !A || !b) return DQP_ERR_BAD_ARG;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (d->has_bounds && (!u_lower || !u_upper)) return DQP_ERR_BAD_ARG;
     MpcP P = {};
     P.C = C; P.c = c; P.F = F; P.f = f; P.x0 = x0; P.ul = u_lower; P.uu = u_upper;
@@ -446,6 +477,10 @@ dqp_mpc_assemble(const dqp_mpc_dims *d, const double *C, const double *c, const 
     const long long nineq = P.bounds ? 2LL * P.T * P.m : P.m;
     const long long total = (long long)P.B * (nz * nz + neq * nz + nineq * nz + nz + neq + nineq);
     DQP_LAUNCH(assemble_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, P);
+    if (P.bounds && dqp::al_bounds_strided(bounds)) {
+        const BoundStrides bs = {bounds->stride_b, bounds->stride_t};
+        DQP_LAUNCH(assemble_bounds_kernel, dim3(grid_for((long long)P.B * nineq)), dim3(256), 0, (hipStream_t)stream, P, bs);
+    }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 

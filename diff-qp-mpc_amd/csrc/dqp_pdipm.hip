@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "dqp_common.h"
+#include "dqp_al_bounds.h"
 #include "dqp_dyn_models.h"
 
 using namespace dqp;
@@ -1012,12 +1013,27 @@ dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C
                    const double *u_upper, double *tau, double *lam, double *nu, double *slack,
                    int32_t *info, double *best_resid, void *workspace, void *termination, void *stream)
 {
+    const dqp_mpc_bounds bounds = {u_lower, u_upper, 0, 0};
+    return dqp_mpc_qp_forward_bounds(md, opts, C, c, F, f, x0, &bounds, tau, lam, nu, slack, info, best_resid, workspace,
+                                     termination, stream);
+}
+
+// the bounds of sample b, knot t, control k at [b stride_b + t stride_t + k] (include/dqp.h: dqp_mpc_bounds).  The padded
+// route passes them through as they are: controls are not padded.
+__attribute__((visibility("default"))) int
+dqp_mpc_qp_forward_bounds(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
+                          const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
+                          double *tau, double *lam, double *nu, double *slack, int32_t *info, double *best_resid,
+                          void *workspace, void *termination, void *stream)
+{
     KParams P = {};
     size_t lds = 0;
     int kind;
     int rc = mpc_params(md, opts, P, lds, kind);
     if (rc != DQP_OK) return rc;
+    if ((rc = mpc_bounds_layout(bounds, md)) != DQP_OK) return rc;
     if (P.B == 0) return DQP_OK;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (!C || !c || !F || !f || !x0 || !u_lower || !u_upper || !tau || !lam || !nu || !slack || !workspace)
         return DQP_ERR_BAD_ARG;
     if (P.dynId && !(P.dynDt > 0.0)) return DQP_ERR_BAD_ARG;        // the model's step needs dqp_opts.dyn_dt
@@ -1025,7 +1041,8 @@ dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C
         if (kind == MPC_PAD) return stage_forward(Q, stream);
         return kind == MPC_R16N ? r16n_forward(Q, stream) : kind == MPC_RICW ? ricw_forward(Q, stream) : ric_forward(Q, stream);
     };
-    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0; P.mul = u_lower; P.muu = u_upper;
+    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0;
+    mpc_set_bounds(P, bounds);
     P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
     P.workspace = (double *)workspace;
     if (P.maxIter < 1) return DQP_ERR_BAD_ARG;
@@ -1103,16 +1120,31 @@ dqp_mpc_qp_forward_stepped(const dqp_mpc_dims *md, const dqp_opts *opts, const d
                            double *tau, double *lam, double *nu, double *slack, int32_t *info, double *best_resid,
                            void *workspace, void *termination, void *stream)
 {
+    const dqp_mpc_bounds bounds = {u_lower, u_upper, 0, 0};
+    return dqp_mpc_qp_forward_stepped_bounds(md, opts, C, c, F, f, x0, &bounds, ext_ry, it_begin, it_end, tau, lam, nu, slack,
+                                             info, best_resid, workspace, termination, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_mpc_qp_forward_stepped_bounds(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
+                                  const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
+                                  const double *ext_ry, int32_t it_begin, int32_t it_end, double *tau, double *lam,
+                                  double *nu, double *slack, int32_t *info, double *best_resid, void *workspace,
+                                  void *termination, void *stream)
+{
     KParams P = {};
     int rc = stepped_params(md, opts, P);
     if (rc != DQP_OK) return rc;
+    if ((rc = mpc_bounds_layout(bounds, md)) != DQP_OK) return rc;
     if (P.B == 0) return DQP_OK;
+    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (!C || !c || !F || !f || !x0 || !u_lower || !u_upper || !tau || !lam || !nu || !slack || !workspace)
         return DQP_ERR_BAD_ARG;
     if (P.maxIter < 1 || it_begin < 0 || it_end < it_begin || it_end > P.maxIter || it_end - it_begin > 1) return DQP_ERR_BAD_ARG;
     if (it_end > it_begin && !ext_ry) return DQP_ERR_BAD_ARG;
     if (it_end == it_begin && it_begin != 0) return DQP_ERR_BAD_ARG;
-    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0; P.mul = u_lower; P.muu = u_upper;
+    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0;
+    mpc_set_bounds(P, bounds);
     P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
     P.workspace = (double *)workspace;
     P.extRy = ext_ry; P.itBegin = it_begin; P.itEnd = it_end;

@@ -479,8 +479,10 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
         }
 #pragma unroll
         for (int s = 0; s < SM; ++s) {
-            const int i = r + 16 * s, k = (i < T * m ? i : i - T * m), ju = (k < T * m ? k : 0) % m;
-            const double v = i < T * m ? P.muu[ju] : -P.mul[ju];
+            // row i: knot t = k / m, control ju = k % m of sample qp in the bound layout (dqp_common.h; (0, 0): the vector)
+            const int i = r + 16 * s, k = (i < T * m ? i : i - T * m), kc = k < T * m ? k : 0, t = kc / m, ju = kc - t * m;
+            const long long at = qp * mpc_bound_stride_b(P) + t * mpc_bound_stride_t(P) + ju;
+            const double v = i < T * m ? P.muu[at] : -P.mul[at];
             h0[s] = i < M ? v : 0.0;
         }
 #pragma unroll

@@ -35,6 +35,7 @@
 
 #include "../../include/dqp.h"
 #include "dqp_common.h"
+#include "dqp_al_bounds.h"
 #include "dqp_r16_prims.h"
 #include "dqp_dyn_models.h"
 
@@ -98,6 +99,17 @@ __host__ __device__ inline Lay layout(int nx, int nu, int T)
 
 enum Mode { INIT = 0, AFFINE = 1, CORRECTOR = 2, ADJOINT = 3 };
 
+// Control bounds per sample and knot (dqp_mpc_qp_forward_bounds): a kernel instantiated on StridedBounds<Cfg<..>> reads
+// the pair of sample b, knot t, control k at [b stride_b + t stride_t + k] (mpc_bound_stride_b / _t of dqp_common.h), once
+// per knot and sweep, in the prefetch of the knot's other vectors; on the plain Cfg the pair is the n_ctrl-vector held
+// in Ctx::uu / ulo for the whole solve and none of this is compiled.  BoundRoot: what a strided context keeps per lane.
+// (Loading the pair at the knot that uses it, instead of one knot ahead, was tried to keep it out of the registers that
+// are live across the Riccati update: the 256-register pairs spilled more, not less -- DESIGN §4.10.b.)
+struct NoBoundRoot {};
+struct BoundRoot { long long off; };      // qp * stride_b
+template <class C, bool SB = strided_bounds<C>::value> struct bound_root { using type = NoBoundRoot; };
+template <class C> struct bound_root<C, true> { using type = BoundRoot; };
+
 extern __shared__ __attribute__((aligned(16))) double lds_dyn[];       // Cfg<., ., true>: [C | F | c | f | four workspaces]
 
 template <class C> struct Ctx {
@@ -115,6 +127,10 @@ template <class C> struct Ctx {
     double *img;                    // the wavefront's LDS stage (Stage<C>); WSL: every knot's C_t, then every F_t
     int rf;                         // WSL: where the F_t images start in img
     const double *lc, *lf;          // WSL: c and f of the Q problems, [(t * Q + place) * NT or NX + r]
+    typename bound_root<C>::type kb;   // strided bounds only (last: the initialisers of the kernels leave it out)
+    // upper / lower bound of this control lane at knot t (strided bounds)
+    __device__ double bnd_up(int t) const { if constexpr (strided_bounds<C>::value) return P.muu[kb.off + (long long)t * mpc_bound_stride_t(P) + a]; else return uu; }
+    __device__ double bnd_lo(int t) const { if constexpr (strided_bounds<C>::value) return P.mul[kb.off + (long long)t * mpc_bound_stride_t(P) + a]; else return ulo; }
     __device__ const double *imgC(int t) const { return C::WSL ? img + t * (C::Q * C::NT * C::NT) : img; }
     __device__ const double *imgF(int t) const;
     __device__ double cvec(int t) const { return C::WSL ? lc[(t * C::Q + g) * C::NT + r] : P.mc[((long long)t * P.B + qp) * C::NT + r]; }
@@ -522,7 +538,9 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
     double pn = 0.0;
     bool ok = true;
     // the knot's vectors: tau_t, c_t, (s, z)_t, y_{t-1} (t = 0: the multiplier of x_0 = x0), f_t, x0
-    enum { V_TAU, V_MC, V_SU, V_SL, V_ZU, V_ZL, V_YP, V_MF, V_X0, V_N };
+    constexpr bool SB = strided_bounds<C>::value;
+    enum { V_TAU, V_MC, V_SU, V_SL, V_ZU, V_ZL, V_YP, V_MF, V_X0, V_UU, V_UL, V_ALL };
+    constexpr int V_N = SB ? (int)V_ALL : (int)V_UU;       // the knot's bound pair only where it varies
     auto load_vec = [&](const Ctx<C> &K, int t, double (&v)[V_N]) {
         const int r = K.r;
         double *w = K.w;
@@ -532,6 +550,7 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
         if (K.ul) {
             const int iu = t * NU + K.a;
             v[V_SU] = w[L.SU + iu]; v[V_SL] = w[L.SL + iu]; v[V_ZU] = w[L.ZU + iu]; v[V_ZL] = w[L.ZL + iu];
+            if constexpr (SB) { v[V_UU] = K.bnd_up(t); v[V_UL] = K.bnd_lo(t); }
         }
         if (K.xl) {
             v[V_YP] = w[L.Y + (t >= 1 ? t - 1 : T - 1) * NX + r];
@@ -564,7 +583,8 @@ __device__ __forceinline__ bool factor_fused(const Ctx<C> &K0, double &nx2, doub
             const int iu = t * NU + K.a;
             const double su = cur[V_SU], sl = cur[V_SL], zu = cur[V_ZU], zl = cur[V_ZL];
             rx += zu - zl;
-            const double rzu = tau - K.uu + su, rzl = -tau + K.ulo + sl;
+            const double bu = SB ? cur[SB ? V_UU : 0] : K.uu, bl = SB ? cur[SB ? V_UL : 0] : K.ulo;
+            const double rzu = tau - bu + su, rzl = -tau + bl + sl;
             w[L.RZU + iu] = rzu; w[L.RZL + iu] = rzl;
             nz2 = fma(rzu, rzu, fma(rzl, rzl, nz2));
             sz = fma(su, zu, fma(sl, zl, sz));
@@ -662,6 +682,8 @@ __device__ __forceinline__ void rhs_load(const Ctx<C> &K, int t, double (&v)[R_N
     for (int i = 0; i < R_N; ++i) v[i] = (i == R_B || i == R_C) ? 1.0 : 0.0;
     if (MODE == INIT) {            // batch.py:60-74: rx = p, rs = 0, rz = -h, ry = -b with d = 1
         if (NEED_Q && r < NT) v[R_A] = K.cvec(t);
+        if constexpr (strided_bounds<C>::value)
+            if (NEED_Q && K.ul) { v[R_D] = K.bnd_up(t); v[R_E] = K.bnd_lo(t); }
         if (NEED_E && K.xl && t < T - 1) v[R_H] = K.fvec(t);
     } else if (MODE == AFFINE) {   // rx, rs = z, rz, ry of the iterate: q_t is formed and used inside factor_fused
         static_assert(!(MODE == AFFINE && NEED_Q), "the affine backward sweep is part of factor_fused");
@@ -680,7 +702,10 @@ __device__ __forceinline__ void rhs_load(const Ctx<C> &K, int t, double (&v)[R_N
 template <class C, int MODE>
 __device__ __forceinline__ double rhs_q(const Ctx<C> &K, const double (&v)[R_N], double musig)
 {
-    if (MODE == INIT) return v[R_A] - (K.ul ? K.uu + K.ulo : 0.0);
+    if (MODE == INIT) {
+        if constexpr (strided_bounds<C>::value) return v[R_A] - (K.ul ? v[R_D] + v[R_E] : 0.0);
+        else return v[R_A] - (K.ul ? K.uu + K.ulo : 0.0);
+    }
     if (MODE == CORRECTOR) return K.ul ? -((-musig + v[R_D] * v[R_E]) * frcp(v[R_B]) - (-musig + v[R_F] * v[R_G]) * frcp(v[R_C])) : 0.0;
     return v[R_A];
 }
@@ -780,6 +805,8 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
         if (K.ul) {
             const int iu = t * NU + K.a;
             v[V_YB] = w[L.YB + iu];
+            if constexpr (strided_bounds<C>::value)
+                if (MODE == INIT) { v[V_A] = K.bnd_up(t); v[V_B] = K.bnd_lo(t); }
             if (MODE == AFFINE || MODE == CORRECTOR) { v[V_SU] = w[L.SU + iu]; v[V_SL] = w[L.SL + iu]; v[V_ZU] = w[L.ZU + iu]; v[V_ZL] = w[L.ZL + iu]; }
             if (MODE == AFFINE) { v[V_A] = w[L.RZU + iu]; v[V_B] = w[L.RZL + iu]; }
             if (MODE == CORRECTOR) { v[V_A] = w[L.DSU + iu]; v[V_B] = w[L.DSL + iu]; v[V_C] = w[L.DZU + iu]; v[V_D] = w[L.DZL + iu]; }
@@ -830,7 +857,8 @@ __device__ __forceinline__ double sweep_fwd(const Ctx<C> &K0, double musig)
         if (K.ul && MODE != ADJOINT) {
             const int iu = t * NU + K.a;
             if (MODE == INIT) {            // s = ds = -rz - G dx,  z = dz = -ds   (d = 1, rs = 0)
-                const double su = K.uu - dtau, sl = dtau - K.ulo;
+                constexpr bool SB = strided_bounds<C>::value;
+                const double su = (SB ? cur[V_A] : K.uu) - dtau, sl = dtau - (SB ? cur[V_B] : K.ulo);
                 w[L.SU + iu] = su; w[L.SL + iu] = sl; w[L.ZU + iu] = -su; w[L.ZL + iu] = -sl;
             } else {
                 const double su = cur[V_SU], sl = cur[V_SL], zu = cur[V_ZU], zl = cur[V_ZL];
@@ -974,7 +1002,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C::WPE, C::W
                 (r >= NX && r < NT) ? r - NX : 0, 0.0, 0.0,
                 lane, lane / G, (int)min((long long)Q - 1, (long long)P.B - 1 - qp0), qp0, ws0, img,
                 S::res_f(T), lds_dyn + S::res_c(T), lds_dyn + S::res_fv(T)};
-    K.uu = P.muu[K.a]; K.ulo = P.mul[K.a];
+    if constexpr (strided_bounds<C>::value) K.kb.off = qp * mpc_bound_stride_b(P);
+    else { K.uu = P.muu[K.a]; K.ulo = P.mul[K.a]; }
     if constexpr (C::WSL) {     // the whole problem into LDS, once
         S::MC::template fetch_all<NT>(img, K.Cblk(0), (long long)P.B * NT * NT * 8, NT * NT * 8, K.qmax, lane, T);
         if (T > 1) S::MF::template fetch_all<NX>(img + K.rf, K.Fblk(0), (long long)P.B * NX * NT * 8, NX * NT * 8, K.qmax, lane, T - 1);
@@ -1243,13 +1272,23 @@ int ric_forward(const KParams &P, void *stream)
     if (P.mn == a && P.mm == b) {                                                                                     \
         using Cg = ric::Cfg<a, b>;                                                                                    \
         using Cl = ric::Cfg<a, b, true>;                                                                              \
+        using Sg = StridedBounds<Cg>;                                                                                 \
+        using Sl = StridedBounds<Cl>;                                                                                 \
+        const bool sbd = mpc_bounds_strided(P);                                                                       \
         const size_t lds = (ric::Stage<Cl>::res_ws(P.mT) + 4 * (size_t)ric::layout(a, b, P.mT).total) * sizeof(double); \
         const bool wsl = !(P.flags & DQP_FLAG_RIC_GLOBAL_WS) && (lds <= 40 * 1024 || (lds <= 64 * 1024 && (P.B + 3) / 4 <= 512)); \
         if constexpr (ric::has_model<Cg>())                                                                           \
-            if (P.dynId)                                                                                              \
+            if (P.dynId) {                                                                                            \
+                if (sbd)                                                                                              \
+                    return wsl ? ric::launch<Cl>(ric::forward_kernel<Sl, ric::RES_MODEL>, P, P.mT, stream, lds)                 \
+                               : ric::launch<Cg>(ric::forward_kernel<Sg, ric::RES_MODEL>, P, P.mT, stream);                     \
                 return wsl ? ric::launch<Cl>(ric::forward_kernel<Cl, ric::RES_MODEL>, P, P.mT, stream, lds)                     \
                            : ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_MODEL>, P, P.mT, stream);                         \
+            }                                                                                                         \
         if (P.dynId) return 1;                                                                                        \
+        if (sbd)                                                                                                      \
+            return wsl ? ric::launch<Cl>(ric::forward_kernel<Sl, ric::RES_LINEAR>, P, P.mT, stream, lds)                        \
+                       : ric::launch<Cg>(ric::forward_kernel<Sg, ric::RES_LINEAR>, P, P.mT, stream);                            \
         return wsl ? ric::launch<Cl>(ric::forward_kernel<Cl, ric::RES_LINEAR>, P, P.mT, stream, lds)                            \
                    : ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_LINEAR>, P, P.mT, stream);                                \
     }
@@ -1266,7 +1305,12 @@ long long ric_stepped_workspace_doubles(int n, int m, int T, int B)
 }
 int ric_forward_stepped(const KParams &P, void *stream)
 {
-#define X(a, b) if (P.mn == a && P.mm == b) return ric::launch<ric::Cfg<a, b>>(ric::forward_kernel<ric::Cfg<a, b>, ric::RES_CALLER>, P, P.mT, stream);
+#define X(a, b)                                                                                                       \
+    if (P.mn == a && P.mm == b) {                                                                                     \
+        using Cg = ric::Cfg<a, b>;                                                                                    \
+        if (mpc_bounds_strided(P)) return ric::launch<Cg>(ric::forward_kernel<StridedBounds<Cg>, ric::RES_CALLER>, P, P.mT, stream); \
+        return ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_CALLER>, P, P.mT, stream);                            \
+    }
     DQP_RIC_SIZES
 #undef X
     return 1;

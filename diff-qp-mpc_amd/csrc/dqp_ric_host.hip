@@ -25,6 +25,9 @@ int DQP_HOST_CAT(ric_host_run_, DQP_RIC_HOST_PART)(int op, const KParams &P, voi
 #define X(a, b)                                                                                               \
     if (P.mn == a && P.mm == b) {                                                                             \
         using Cg = ric::Cfg<a, b>;                                                                            \
+        using Sg = StridedBounds<Cg>;                                                                         \
+        if (op == RIC_HOST_FORWARD && mpc_bounds_strided(P)) return ric::launch<Cg>(ric::forward_kernel<Sg, ric::RES_LINEAR>, P, P.mT, stream); \
+        if (op == RIC_HOST_STEPPED && mpc_bounds_strided(P)) return ric::launch<Cg>(ric::forward_kernel<Sg, ric::RES_CALLER>, P, P.mT, stream); \
         if (op == RIC_HOST_FORWARD) return ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_LINEAR>, P, P.mT, stream); \
         if (op == RIC_HOST_STEPPED) return ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_CALLER>, P, P.mT, stream); \
         return ric::launch<Cg>(ric::backward_kernel<Cg>, P, P.mT, stream);                                    \

@@ -35,7 +35,12 @@ long long ricw_workspace_doubles(int n, int m, int T)
 int ricw_forward(const KParams &P, void *stream)
 {
     if (P.dynId) return 1;
-#define X(a, b) if (P.mn == a && P.mm == b) return ric::launch<ric::Cfg<a, b>>(ric::forward_kernel<ric::Cfg<a, b>, ric::RES_LINEAR>, P, P.mT, stream);
+#define X(a, b)                                                                                                       \
+    if (P.mn == a && P.mm == b) {                                                                                     \
+        using Cg = ric::Cfg<a, b>;                                                                                    \
+        if (mpc_bounds_strided(P)) return ric::launch<Cg>(ric::forward_kernel<StridedBounds<Cg>, ric::RES_LINEAR>, P, P.mT, stream); \
+        return ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_LINEAR>, P, P.mT, stream);                            \
+    }
     DQP_RICW_SIZES
 #undef X
     return 1;
@@ -50,7 +55,12 @@ long long ricw_stepped_workspace_doubles(int n, int m, int T, int B)
 
 int ricw_forward_stepped(const KParams &P, void *stream)
 {
-#define X(a, b) if (P.mn == a && P.mm == b) return ric::launch<ric::Cfg<a, b>>(ric::forward_kernel<ric::Cfg<a, b>, ric::RES_CALLER>, P, P.mT, stream);
+#define X(a, b)                                                                                                       \
+    if (P.mn == a && P.mm == b) {                                                                                     \
+        using Cg = ric::Cfg<a, b>;                                                                                    \
+        if (mpc_bounds_strided(P)) return ric::launch<Cg>(ric::forward_kernel<StridedBounds<Cg>, ric::RES_CALLER>, P, P.mT, stream); \
+        return ric::launch<Cg>(ric::forward_kernel<Cg, ric::RES_CALLER>, P, P.mT, stream);                            \
+    }
     DQP_RICW_SIZES
 #undef X
     return 1;

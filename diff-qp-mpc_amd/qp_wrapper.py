@@ -30,6 +30,7 @@ from torch.autograd import Function
 from torch.nn import Module
 
 from . import _lib
+from .al_utils import mpc_bounds_layout
 from .dynamics import DeviceDynamics, DynamicsResidual
 from .qp import DenseQPFunction
 
@@ -99,20 +100,18 @@ class _AssembleDenseQP(Function):
         nineq = 2 * T * n_ctrl if bounds else n_ctrl
         cv = lambda t: t.detach().double().contiguous()
         Cc, cc, Fc, fc, xc = cv(C), cv(c), cv(F), cv(f), cv(x0)
-        ul = cv(u_lower).reshape(-1) if bounds else None
-        uu = cv(u_upper).reshape(-1) if bounds else None
-        if bounds and (ul.numel() != n_ctrl or uu.numel() != n_ctrl):
-            raise RuntimeError("u_lower/u_upper must have shape (n_ctrl,) (qp_wrapper.py:677-678)")
+        # per-sample / per-knot bounds in their own layout (al_utils.mpc_bounds_layout names the accepted shapes)
+        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl) if bounds else _lib.dqp_al_bounds(None, None, 0, 0)
         kw = dict(dtype=torch.float64, device=dev)
         Q = torch.empty(B, nz, nz, **kw); p = torch.empty(B, nz, **kw)
         G = torch.empty(B, nineq, nz, **kw); h = torch.empty(B, nineq, **kw)
         A = torch.empty(B, neq, nz, **kw); b = torch.empty(B, neq, **kw)
         dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1 if bounds else 0, 0)
         with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_assemble(ctypes.byref(dims), _ptr(Cc), _ptr(cc), _ptr(Fc), _ptr(fc),
-                                      _ptr(xc), _ptr(ul), _ptr(uu), _ptr(Q), _ptr(p), _ptr(G),
-                                      _ptr(h), _ptr(A), _ptr(b), _stream(dev))
-        _lib.check(rc, "dqp_mpc_assemble")
+            rc = lib.dqp_mpc_assemble_bounds(ctypes.byref(dims), _ptr(Cc), _ptr(cc), _ptr(Fc), _ptr(fc),
+                                             _ptr(xc), bl.ref() if bounds else ctypes.byref(bl), _ptr(Q), _ptr(p), _ptr(G),
+                                             _ptr(h), _ptr(A), _ptr(b), _stream(dev))
+        _lib.check(rc, "dqp_mpc_assemble_bounds")
         ctx.dims = dims
         ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
         ctx.dtype = x0.dtype
@@ -169,9 +168,8 @@ class _MPCQP(Function):
                                    "there is no CPU fallback.")
         dev, B, nt = x0.device, x0.shape[0], n_state + n_ctrl
         cv = lambda t: t.detach().double().contiguous()
-        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0), cv(u_lower).reshape(-1), cv(u_upper).reshape(-1)]
-        if keep[5].numel() != n_ctrl or keep[6].numel() != n_ctrl:
-            raise RuntimeError("u_lower/u_upper must have shape (n_ctrl,) (qp_wrapper.py:677-678)")
+        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
+        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl)      # per sample / per knot: names the accepted shapes
         # dyn: a DeviceDynamics whose true step is the equality residual of the iterations (the reference's
         # dyn_res closure, qp_wrapper.py:309,316); F, f stay the linearisation the Newton steps use
         dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, dyn.id if dyn is not None else 0, n_state_host)
@@ -189,10 +187,10 @@ class _MPCQP(Function):
         tb = int(lib.dqp_mpc_qp_termination_bytes(ctypes.byref(dims), ctypes.byref(opts)))
         term = torch.empty((tb + 7) // 8, **kw) if tb else None
         with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_qp_forward(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep],
-                                        _ptr(tau), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(info), _ptr(resid),
-                                        _ptr(ws), _ptr(term), _stream(dev))
-        _lib.check(rc, "dqp_mpc_qp_forward")
+            rc = lib.dqp_mpc_qp_forward_bounds(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep], bl.ref(),
+                                               _ptr(tau), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(info), _ptr(resid),
+                                               _ptr(ws), _ptr(term), _stream(dev))
+        _lib.check(rc, "dqp_mpc_qp_forward_bounds")
         ctx.dims, ctx.ws = dims, ws
         ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
         ctx.dtype = x0.dtype
@@ -249,9 +247,8 @@ class _MPCQPStepped(Function):
         lib = _lib.load()
         dev, B, nt = x0.device, x0.shape[0], n_state + n_ctrl
         cv = lambda t: t.detach().double().contiguous()
-        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0), cv(u_lower).reshape(-1), cv(u_upper).reshape(-1)]
-        if keep[5].numel() != n_ctrl or keep[6].numel() != n_ctrl:
-            raise RuntimeError("u_lower/u_upper must have shape (n_ctrl,) (qp_wrapper.py:677-678)")
+        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
+        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl)      # per sample / per knot: names the accepted shapes
         nh = _MPCQPStepped.host_n_state(B, n_state, n_ctrl, T)
         if nh < 0:
             raise NotImplementedError("no stage-wise kernels for (n_state, n_ctrl) = (%d, %d)" % (n_state, n_ctrl))
@@ -271,10 +268,11 @@ class _MPCQPStepped(Function):
 
         def call(ry, it0, it1):
             with torch.cuda.device(dev):
-                rc = lib.dqp_mpc_qp_forward_stepped(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep], _ptr(ry),
-                                                    it0, it1, _ptr(tau), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(info),
-                                                    _ptr(resid), _ptr(ws), _ptr(term), _stream(dev))
-            _lib.check(rc, "dqp_mpc_qp_forward_stepped")
+                rc = lib.dqp_mpc_qp_forward_stepped_bounds(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep],
+                                                           bl.ref(), _ptr(ry), it0, it1, _ptr(tau), _ptr(lam), _ptr(nu),
+                                                           _ptr(slack), _ptr(info), _ptr(resid), _ptr(ws), _ptr(term),
+                                                           _stream(dev))
+            _lib.check(rc, "dqp_mpc_qp_forward_stepped_bounds")
 
         with torch.no_grad():
             call(None, 0, 0)                                    # starting point -> tau
@@ -362,6 +360,13 @@ class MPC(Module):
     (qp_wrapper.py:124-150); options it accepts but never reads (delta_u, back_eps,
     exit_unconverged, detach_unconverged, backprop, slew_rate_penalty, prev_ctrl, u_zero_I) are
     accepted and stored likewise.
+
+    Control bounds: a float, or a tensor of shape (n_ctrl,), (T, n_ctrl), (T, 1, n_ctrl), (1, n_batch, n_ctrl) or
+    (T, n_batch, n_ctrl) -- time-major like every other tensor here; both bounds of one shape (al_utils.mpc_bounds_layout).
+    The kernels index the tensor as it is: nothing is expanded, and an fp64 contiguous tensor is not copied.  Per-sample
+    bounds are (1, n_batch, n_ctrl); (n_batch, n_ctrl) is refused, it cannot be told from (T, n_ctrl).  Every pair must
+    satisfy lower < upper; this is not checked (it would be a host synchronisation), and the interior-point iteration has
+    no interior at lower == upper.  Bounds carry no gradient.
     """
 
     def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, u_zero_I=None,

@@ -49,6 +49,10 @@ class MPC(qp_wrapper.MPC):
                                       "dynamics rows only (sl1qp_mpc.py:723-751)")
         if u_lower is None:
             raise NotImplementedError("the l1-slack form needs control bounds (its G block, sl1qp_mpc.py:693-700)")
+        for v in (u_lower, u_upper):
+            if torch.is_tensor(v) and v.numel() != n_ctrl:
+                raise ValueError("sl1qp_mpc.MPC takes control bounds of shape (n_ctrl,) only (got %s): per-sample and "
+                                 "per-knot bounds are a feature of qp_wrapper.MPC and AL_mpc.MPC" % (tuple(v.shape),))
         super().__init__(n_state, n_ctrl, T, u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, u_init=u_init,
                          x_init=x_init, qp_iter=qp_iter, grad_method=grad_method, delta_u=delta_u, verbose=verbose,
                          eps=eps, back_eps=back_eps, n_batch=n_batch, linesearch_decay=linesearch_decay,

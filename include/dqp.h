@@ -280,6 +280,8 @@ typedef struct dqp_mpc_dims {
  * Inputs are the reference's time-major tensors C (T,B,nt,nt) c (T,B,nt) F (T-1,B,n,nt)
  * f (T-1,B,n) x0 (B,n) and the control bounds u_lower/u_upper (n_ctrl,) (ignored without
  * bounds).  Outputs are the dense batch-major QP (Q,p,G,h,A,b) that dqp_qp_forward consumes.
+ * Bounds that differ per sample or per knot: dqp_mpc_assemble_bounds ("Per-sample, per-knot control bounds of the MPC
+ * QP" below); this entry point is that twin at strides (0, 0).
  */
 int dqp_mpc_assemble(const dqp_mpc_dims *dims, const double *C, const double *c, const double *F,
                      const double *f, const double *x0, const double *u_lower,
@@ -328,6 +330,8 @@ int dqp_mpc_assemble_backward(const dqp_mpc_dims *dims, const double *dQ, const 
  * into the workspace; the later calls of the solve read that copy.
  * tau (B, T, n_state+n_ctrl) = the QP solution per knot [x_t, u_t]; lam/nu/slack/info/best_resid and
  * the termination modes as in dqp_qp_forward; backward = DenseQPFunction's (un-clamped d).
+ * u_lower/u_upper (n_ctrl,) hold for every sample and knot; dqp_mpc_qp_forward_bounds takes them per sample and per knot
+ * (dqp_mpc_qp_forward is that twin at strides (0, 0)).  The backward reads no bounds.
  */
 int dqp_mpc_qp_supported(const dqp_mpc_dims *dims);
 size_t dqp_mpc_qp_workspace_bytes(const dqp_mpc_dims *dims);
@@ -362,6 +366,8 @@ int dqp_mpc_qp_backward(const dqp_mpc_dims *dims, const dqp_opts *opts, const do
  * returned best iterate and its multipliers in tau, lam, nu, slack.  All solver state between calls lives in
  * `workspace` (dqp_mpc_qp_stepped_workspace_bytes: always the caller's buffer) and `termination`.
  * Shapes: the stage-wise pairs of dqp_mpc_qp_forward (compiled (n_state, n_ctrl), n_state + n_ctrl <= 32).
+ * Bounds per sample and per knot: dqp_mpc_qp_forward_stepped_bounds (this entry point is that twin at strides (0, 0));
+ * every call of one solve passes the same bounds.
  */
 size_t dqp_mpc_qp_stepped_workspace_bytes(const dqp_mpc_dims *dims);
 size_t dqp_mpc_qp_stepped_termination_bytes(const dqp_mpc_dims *dims, const dqp_opts *opts);
@@ -662,6 +668,48 @@ int dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *dims, const doub
                                          const double *Qdiag, const double *q, const double *lam, const double *rho,
                                          const dqp_al_bounds *bounds, const double *x_next, const double *Jx,
                                          const double *Ju, double *update, void *factor, int32_t *info, void *stream);
+
+/*
+ * Per-sample, per-knot control bounds of the MPC QP (additive at 303).  dqp_mpc_assemble, dqp_mpc_qp_forward and
+ * dqp_mpc_qp_forward_stepped read one vector of n_ctrl bounds for the whole batch and horizon.  Their `_bounds` twins take
+ * a dqp_mpc_bounds -- the struct of the AL twins above -- in the position of the (u_lower, u_upper) pair, every other
+ * argument unchanged, and read lower / upper [b * stride_b + t * stride_t + k] for sample b, knot t, control k.  With
+ * m = n_ctrl, B = nbatch the accepted (stride_b, stride_t) are
+ *
+ *     (0, 0)        m doubles        the vector form: the twin launches exactly the kernels of the old entry point,
+ *                                    which is itself the twin at (0, 0)
+ *     (0, m)        (T, m)           per knot, the same for every sample
+ *     (m, 0)        (B, m)           per sample, constant along the horizon
+ *     (m, B m)      (T, B, m)        per sample and knot, time-major like C, c, F, f
+ *     (T m, m)      (B, T, m)        per sample and knot, batch-major: the full layout of the AL twins, so one buffer
+ *                                    serves both solver families
+ *
+ * Anything else, a null struct, or (at nbatch > 0) a null lower / upper is DQP_ERR_BAD_ARG; struct and strides are checked
+ * in front of the nbatch == 0 return.  lower < upper is required of every pair and not checked: the interior-point
+ * iteration has no interior at lower == upper.  Inequality rows keep their order [u - upper (T m, knot-major) ;
+ * lower - u (T m)].  dqp_mpc_qp_supported, _workspace_bytes, _termination_bytes, _host_n_state and the stepped sizes do
+ * not depend on the layout (the kernels read the bounds from the caller's arrays, nothing is staged), and
+ * dqp_mpc_qp_backward reads no bounds: none of them has a twin.
+ *
+ * Kernels: the stage-wise forward kernels (16-lane, wide and host-only pairs; LDS-resident and streamed; linear,
+ * registered-model and caller residual) have a strided instantiation next to the vector one, taken at non-zero strides
+ * only; it loads a knot's pair with the knot's other vectors.  The null-space kernels and the assembly read the layout
+ * in their one set-up pass over h.
+ */
+typedef dqp_al_bounds dqp_mpc_bounds;
+
+int dqp_mpc_assemble_bounds(const dqp_mpc_dims *dims, const double *C, const double *c, const double *F,
+                            const double *f, const double *x0, const dqp_mpc_bounds *bounds, double *Q, double *p,
+                            double *G, double *h, double *A, double *b, void *stream);
+int dqp_mpc_qp_forward_bounds(const dqp_mpc_dims *dims, const dqp_opts *opts, const double *C, const double *c,
+                              const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
+                              double *tau, double *lam, double *nu, double *slack, int32_t *info, double *best_resid,
+                              void *workspace, void *termination, void *stream);
+int dqp_mpc_qp_forward_stepped_bounds(const dqp_mpc_dims *dims, const dqp_opts *opts, const double *C, const double *c,
+                                      const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
+                                      const double *ext_ry, int32_t it_begin, int32_t it_end, double *tau, double *lam,
+                                      double *nu, double *slack, int32_t *info, double *best_resid, void *workspace,
+                                      void *termination, void *stream);
 
 /* ----------------------------------------------------------------- device dynamics registry */
 

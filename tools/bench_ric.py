@@ -4,7 +4,11 @@ n_state 12, n_ctrl 4, T 30 (nz 480, nineq 240, neq 360), B = 8192 (BATCH), HIP e
 C-ABI calls dqp_mpc_qp_forward / dqp_mpc_qp_backward, both termination modes.
 HOST=n': the problem padded onto the kernels of (n', m) (dqp_mpc_dims.n_state_host), with the per-kernel split of one
 forward and backward (pack / solve / unpack).  DENSE=1: also assemble + DenseQPFunction on the same data (forward and
-backward, per-problem termination), the route the dense kernels give where nz <= 512."""
+backward, per-problem termination), the route the dense kernels give where nz <= 512.
+--bounds: only the comparison of the per-sample, per-knot bound layout with the vector one -- the same limits as an
+(n_ctrl,) vector and as a (T, B, n_ctrl) tensor through qp_wrapper._MPCQP forward + backward (what qp_wrapper.MPC runs per
+QP), 30 calls each, alternating; median and quartiles.  DYN=name: with that registered model's residual (config 2:
+N=3 M=1 T=10 BATCH=1024 DYN=pendulum_dx)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -34,6 +38,30 @@ ws = torch.empty(wsb // 8, **kw)
 P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
 g = torch.ones(B, T, nt, **kw)
 dC, dc, dF, df, dx0 = torch.empty_like(C), torch.empty_like(c), torch.empty_like(F), torch.empty_like(f), torch.empty_like(x0)
+if "--bounds" in sys.argv[1:]:
+    from diff_qp_mpc_amd import qp_wrapper
+    from diff_qp_mpc_amd.dynamics import DeviceDynamics
+    dyn = DeviceDynamics(os.environ["DYN"]) if os.environ.get("DYN") else None
+    ins = [t.detach().clone().requires_grad_() for t in (C, c, F, f, x0)]
+    pairs = {"vector": (lo, hi), "(T, B, m)": (lo.expand(T, B, m).contiguous(), hi.expand(T, B, m).contiguous())}
+    def call(k):
+        z = qp_wrapper._MPCQP.apply(*ins, *pairs[k], n, m, T, dyn)
+        z.backward(g)
+    ms = {k: [] for k in pairs}
+    for k in pairs:
+        call(k); call(k)
+    torch.cuda.synchronize()
+    for _ in range(30):
+        for k in pairs:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); call(k); b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    print("B=%d n=%d m=%d T=%d dyn=%s: _MPCQP forward + backward, 30 calls each, alternating" % (B, n, m, T, os.environ.get("DYN")))
+    for k, v in ms.items():
+        q1, q2, q3 = np.percentile(v, [25, 50, 75])
+        print("  bounds %-10s median %.3f ms   quartiles %.3f .. %.3f" % (k, q2, q1, q3))
+    sys.exit(0)
 print("B=%d n=%d m=%d T=%d  nz=%d  workspace %.0f MB  inputs %.0f MB" % (B, n, m, T, T * nt, wsb / 1e6, (C.numel() + F.numel()) * 8 / 1e6))
 
 
