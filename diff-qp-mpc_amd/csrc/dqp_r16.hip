@@ -318,8 +318,7 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
         for (int s = 0; s < SE; ++s) mb[s] = -bt[s];
         kkt_rhs<C>(st, ph, zero, mh, mb, wz, r);
         __builtin_amdgcn_sched_barrier(0);
-        factor_T<C>(lds, T, st.rdiag, one, rdu, r);
-        lu_solve<SM, M>(T, rdu, wz, r);
+        factor_T_rhs<C>(lds, T, st.rdiag, one, rdu, wz, r);
         __builtin_amdgcn_sched_barrier(0);
         double gt0[SN], at0[SN];
         kkt_xy<C>(st, ph, mb, wz, xh, yt, gt0, at0, r);
@@ -414,8 +413,9 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
                        !(fabs(resid) < INFINITY))
                 done = true;
         }
-        // the wave leaves when all four of its QPs are done
-        if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+        // the wave leaves when all four of its QPs are done -- or before the last step: nothing reads the
+        // iterate after the last residual (best iterate, iters, history and snapshots are all written above)
+        if (__builtin_amdgcn_ballot_w64(!done) == 0 || it + 1 >= maxIter) break;
         if (it == 1) STAMP(P, 9);
 
         // phase 1 (Gh/At live, T dead): affine right-hand side (rs = z => rs/d = s)
@@ -430,9 +430,8 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
         double dinv[SM];
 #pragma unroll
         for (int s = 0; s < SM; ++s) dinv[s] = inM[s] ? s_[s] * frcp(z[s]) : 0.0;   // 1/d, d = z/s
-        factor_T<C>(lds, T, st.rdiag, dinv, rdu, r);
+        factor_T_rhs<C>(lds, T, st.rdiag, dinv, rdu, dza, r);     // (the affine L sweep rides in the factorisation)
         if (it == 1) STAMP(P, 10);
-        lu_solve<SM, M>(T, rdu, dza, r);
         double rzv[SM], rsv[SM];           // formed only now: not live across the factorisation
 #pragma unroll
         for (int s = 0; s < SM; ++s) {
@@ -582,8 +581,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P)
     __builtin_amdgcn_sched_barrier(0);
     {
         double T[SM][M], rdu[SM];
-        factor_T<C>(lds, T, st.rdiag, dinv, rdu, r);
-        lu_solve<SM, M>(T, rdu, dlam, r);
+        factor_T_rhs<C>(lds, T, st.rdiag, dinv, rdu, dlam, r);
     }
     __builtin_amdgcn_sched_barrier(0);
     double gtd[SN], atd[SN];

@@ -276,17 +276,44 @@ __device__ __forceinline__ bool chol_rows(double (&L)[S][N], double (&rd)[S], in
     return ok;
 }
 
+// Build-time A/B switches of the factorisation (both default on; -DDQP_LU_LOOKAHEAD=0 / -DDQP_LU_FOLD_RHS=0
+// give the plain forms, bit-identical in their results).
+#ifndef DQP_LU_LOOKAHEAD
+#define DQP_LU_LOOKAHEAD 1
+#endif
+#ifndef DQP_LU_FOLD_RHS
+#define DQP_LU_FOLD_RHS 1
+#endif
+
+// ties the scheduling of two independent values together: whatever consumes the outputs comes after
+// everything that produced either input (the look-ahead pivot chain is spread over the trailing
+// column updates this way -- the scheduler would otherwise pull the chain together again)
+#define PIN2(x, y) asm volatile("" : "+v"(x), "+v"(y))
+
 // Unpivoted LU of the row-distributed matrix (in place: unit-lower multipliers below the
 // diagonal, U on/above).  rdu[s] = 1/U[i][i].
-template <int S, int N>
-__device__ __forceinline__ void lu_rows(double (&T)[S][N], double (&rdu)[S], int r)
+//
+// Look-ahead (LA): step k updates column k+1 first and takes the next pivot's reciprocal from it --
+// broadcast, v_rcp_f64 and the four refinement FMAs of frcp, one link after each of the following
+// column updates -- so the chain's latency and the DPP-after-VALU wait states hide under the rest
+// of the trailing update instead of standing in front of step k+1.  Same operations on the same
+// values as the plain order.
+//
+// RHS: the L sweep of lu_solve (L y = b) rides along as one more column of the trailing update,
+// with lu_solve's own expressions and masks: at step k < N-1, b[s] = fma(-L[s][k], bcast(b[k]), b[s]).
+// For a right-hand side known before the factorisation this takes the sweep's N-1 dependent
+// broadcast+FMA links off the critical path; lu_solve_U finishes the solve.
+template <int S, int N, bool RHS, bool LA>
+__device__ __forceinline__ void lu_rows_impl(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
 {
 #pragma unroll
     for (int s = 0; s < S; ++s) rdu[s] = 0.0;
+    double rp = 0.0;
+    if (LA) rp = frcp(rb(T[0][0], 0));
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const int sk = k >> 4, lk = k & 15;
-        const double rp = frcp(rb(T[sk][k], lk));
+        if (!LA) rp = frcp(rb(T[sk][k], lk));
         if (r == lk) rdu[sk] = rp;
         PIN(rdu[sk]);
         double l[S];
@@ -296,19 +323,78 @@ __device__ __forceinline__ void lu_rows(double (&T)[S][N], double (&rdu)[S], int
             else if (16 * s > k) { l[s] = T[s][k] * rp; T[s][k] = l[s]; }
             else { const bool a = r > lk; l[s] = mask_hi(T[s][k], a) * rp; T[s][k] = a ? l[s] : T[s][k]; }
         }
+        // the next pivot's chain: d (stage 0) -> rcp estimate -> e, refined -> e, refined
+        double pd = 0.0, pr = 0.0, pe = 0.0;
+        int stage = 0;
 #pragma unroll
         for (int j = k + 1; j < N; ++j) {
             const double ub = rb(T[sk][j], lk);
 #pragma unroll
             for (int s = 0; s < S; ++s)
                 if (16 * s + 15 > k) T[s][j] = fma(-l[s], ub, T[s][j]);
+            if (RHS && j == k + 1) {                   // L y = b, step k (lu_solve's expressions)
+                const double bk = BC(b, k);
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    if (16 * s + 15 <= k) continue;
+                    if (16 * s > k) b[s] = fma(-T[s][k], bk, b[s]);
+                    else b[s] = fma(-mask_hi(T[s][k], r > lk), bk, b[s]);
+                }
+            }
+            if (LA && j >= k + 2 && stage < 6) {       // one link per column from k+2 on
+                double &tj = T[S - 1][j];              // (a slot that every step still updates)
+                if (stage == 0) { PIN2(tj, T[(k + 1) >> 4][k + 1]); pd = rb(T[(k + 1) >> 4][k + 1], (k + 1) & 15); }
+                else if (stage == 1) { PIN2(tj, pd); pr = __builtin_amdgcn_rcp(pd); }
+                else if (stage & 1) { PIN2(tj, pe); pr = fma(pe, pr, pr); }
+                else { PIN2(tj, pr); pe = fma(-pd, pr, 1.0); }
+                ++stage;
+            }
+        }
+        if (LA && k + 1 < N) {                         // what the remaining columns were too few for
+            if (stage == 0) { pd = rb(T[(k + 1) >> 4][k + 1], (k + 1) & 15); ++stage; }
+            if (stage == 1) { pr = __builtin_amdgcn_rcp(pd); ++stage; }
+#pragma unroll
+            for (; stage < 6; ++stage) {
+                if (stage & 1) pr = fma(pe, pr, pr);
+                else pe = fma(-pd, pr, 1.0);
+            }
+            rp = pr;
         }
     }
 }
 
-// b <- T^-1 b with the LU above.  In the U sweep a lane keeps its own y_k unscaled (the pivot
-// scaling is applied to the broadcast copy and, once, to the whole vector at the end), so the
+template <int S, int N>
+__device__ __forceinline__ void lu_rows(double (&T)[S][N], double (&rdu)[S], int r)
+{
+    double none[S];            // lu_rows_impl<RHS = false> never touches b: dead after inlining
+#pragma unroll
+    for (int s = 0; s < S; ++s) none[s] = 0.0;
+    lu_rows_impl<S, N, false, DQP_LU_LOOKAHEAD != 0>(T, rdu, none, r);
+}
+
+// b <- U^-1 y: the U sweep and the final scaling of lu_solve.  A lane keeps its own y_k unscaled (the
+// pivot scaling is applied to the broadcast copy and, once, to the whole vector at the end), so the
 // only per-step predication is the one-instruction triangle mask.
+template <int S, int N>
+__device__ __forceinline__ void lu_solve_U(const double (&T)[S][N], const double (&rdu)[S],
+                                           double (&b)[S], int r)
+{
+#pragma unroll
+    for (int k = N - 1; k >= 0; --k) {                 // U x = y
+        const int sk = k >> 4, lk = k & 15;
+        const double xk = rb(b[sk] * rdu[sk], lk);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (16 * s > k) continue;
+            if (16 * s + 15 < k) b[s] = fma(-T[s][k], xk, b[s]);
+            else b[s] = fma(-mask_hi(T[s][k], r < lk), xk, b[s]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) b[s] *= rdu[s];
+}
+
+// b <- T^-1 b with the LU above.
 template <int S, int N>
 __device__ __forceinline__ void lu_solve(const double (&T)[S][N], const double (&rdu)[S],
                                          double (&b)[S], int r)
@@ -324,19 +410,28 @@ __device__ __forceinline__ void lu_solve(const double (&T)[S][N], const double (
             else b[s] = fma(-mask_hi(T[s][k], r > lk), bk, b[s]);
         }
     }
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {                 // U x = y
-        const int sk = k >> 4, lk = k & 15;
-        const double xk = rb(b[sk] * rdu[sk], lk);
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            if (16 * s > k) continue;
-            if (16 * s + 15 < k) b[s] = fma(-T[s][k], xk, b[s]);
-            else b[s] = fma(-mask_hi(T[s][k], r < lk), xk, b[s]);
-        }
+    lu_solve_U<S, N>(T, rdu, b, r);
+}
+
+// lu_rows, and b <- L^-1 b along the way (lu_solve_U completes b <- T^-1 b)
+template <int S, int N>
+__device__ __forceinline__ void lu_rows_rhs(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
+{
+    lu_rows_impl<S, N, true, DQP_LU_LOOKAHEAD != 0>(T, rdu, b, r);
+}
+
+// factor + solve for a right-hand side known before the factorisation: b <- T^-1 b.  The callers pass
+// FOLD = (DQP_LU_FOLD_RHS != 0); false is the plain pair lu_rows + lu_solve.
+template <int S, int N, bool FOLD>
+__device__ __forceinline__ void lu_factor_solve(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
+{
+    if (FOLD) {
+        lu_rows_rhs<S, N>(T, rdu, b, r);
+        lu_solve_U<S, N>(T, rdu, b, r);
+    } else {
+        lu_rows<S, N>(T, rdu, r);
+        lu_solve<S, N>(T, rdu, b, r);
     }
-#pragma unroll
-    for (int s = 0; s < S; ++s) b[s] *= rdu[s];
 }
 
 // b <- L^-1 b, L lower triangular row-distributed in registers (rd = reciprocal diagonal)
@@ -519,13 +614,12 @@ __device__ __forceinline__ void load_rows(const double *src, int nrows, double (
 
 // ------------------------------------------------------------------ Schur complement factor
 // (C: a kernel Cfg with M, SM, oR, oDummy)
-// T = R + diag(dinv) (full square, row-distributed) from the packed triangle in LDS, then LU.
+// T = R + diag(dinv) (full square, row-distributed) from the packed triangle in LDS (load_T), then LU.
 // Each lane first rewrites its own diagonal entries of the LDS triangle with R_ii + dinv_i (only
 // the owning lane ever reads them back), so the load needs no per-element diagonal select.
 template <class C>
-__device__ __forceinline__ void factor_T(double *lds, double (&T)[C::SM][C::M],
-                                         const double (&rdiag)[C::SM], const double (&dinv)[C::SM],
-                                         double (&rdu)[C::SM], int r)
+__device__ __forceinline__ void load_T(double *lds, double (&T)[C::SM][C::M],
+                                       const double (&rdiag)[C::SM], const double (&dinv)[C::SM], int r)
 {
     constexpr int M = C::M, SM = C::SM;
     double *Rp = lds + C::oR;
@@ -549,7 +643,25 @@ __device__ __forceinline__ void factor_T(double *lds, double (&T)[C::SM][C::M],
             T[s][j] = (16 * s + 15 >= M) ? mask_hi(v, i < M) : v;       // pad rows: ~zero rows
         }
     }
-    lu_rows<SM, M>(T, rdu, r);
+}
+
+template <class C>
+__device__ __forceinline__ void factor_T(double *lds, double (&T)[C::SM][C::M],
+                                         const double (&rdiag)[C::SM], const double (&dinv)[C::SM],
+                                         double (&rdu)[C::SM], int r)
+{
+    load_T<C>(lds, T, rdiag, dinv, r);
+    lu_rows<C::SM, C::M>(T, rdu, r);
+}
+
+// factor_T and b <- T^-1 b in one (the L sweep inside the factorisation)
+template <class C>
+__device__ __forceinline__ void factor_T_rhs(double *lds, double (&T)[C::SM][C::M],
+                                             const double (&rdiag)[C::SM], const double (&dinv)[C::SM],
+                                             double (&rdu)[C::SM], double (&b)[C::SM], int r)
+{
+    load_T<C>(lds, T, rdiag, dinv, r);
+    lu_factor_solve<C::SM, C::M, DQP_LU_FOLD_RHS != 0>(T, rdu, b, r);
 }
 
 }  // namespace r16

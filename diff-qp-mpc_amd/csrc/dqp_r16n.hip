@@ -1048,8 +1048,7 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
 #pragma unroll
         for (int s = 0; s < SM; ++s) g[s] = inM[s] ? -hp[s] - g[s] : 0.0;
         __builtin_amdgcn_sched_barrier(0);
-        factor_T<C>(lds, T, st.rdiag, one, rdu, r);
-        lu_solve<SM, M>(T, rdu, g, r);
+        factor_T_rhs<C>(lds, T, st.rdiag, one, rdu, g, r);
         __builtin_amdgcn_sched_barrier(0);
         mul_GzT<C>(st, g, gtz, r);
 #pragma unroll
@@ -1080,7 +1079,8 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
     bool have_best = false, done = false;
     int nNot = 0, iters = 0;
 
-    for (int it = 0; it < maxIter; ++it) {
+    // one exit, below the bookkeeping: a second one at the top of the loop costs the fully unrolled body registers
+    if (maxIter > 0) for (int it = 0;; ++it) {
         // residuals                                                        batch.py:93-108
         double rw[SR], rz[SM];
         {
@@ -1128,8 +1128,9 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
                        !(fabs(resid) < INFINITY))
                 done = true;
         }
-        // the wave leaves when all four of its QPs are done
-        if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+        // the wave leaves when all four of its QPs are done -- or before the last step: nothing reads the
+        // iterate after the last residual (best iterate, iters, history and snapshots are all written above)
+        if (__builtin_amdgcn_ballot_w64(!done) == 0 || it + 1 >= maxIter) break;
         if (it == 1) STAMP(P, 9);
 
         // phase 1 (Gz live, T dead): affine right-hand side  g = rz - rs/d - Gz rw,  rs/d = s
@@ -1145,9 +1146,8 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
         double dinv[SM];
 #pragma unroll
         for (int s = 0; s < SM; ++s) dinv[s] = inM[s] ? s_[s] * frcp(z[s]) : 0.0;   // 1/d, d = z/s
-        factor_T<C>(lds, T, st.rdiag, dinv, rdu, r);
+        factor_T_rhs<C>(lds, T, st.rdiag, dinv, rdu, dza, r);     // (the affine L sweep rides in the factorisation)
         if (it == 1) STAMP(P, 10);
-        lu_solve<SM, M>(T, rdu, dza, r);
         if (it == 1) STAMP(P, 11);
         double rzv[SM], rsv[SM];           // formed only now: not live across the factorisation
 #pragma unroll
@@ -1419,8 +1419,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P)
             for (int s = 0; s < SM; ++s) T[s][j] = acc[s];
             __builtin_amdgcn_sched_barrier(0);
         }
-        lu_rows<SM, M>(T, rdu, r);
-        lu_solve<SM, M>(T, rdu, dlam, r);
+        lu_factor_solve<SM, M, DQP_LU_FOLD_RHS != 0>(T, rdu, dlam, r);
     }
     __builtin_amdgcn_sched_barrier(0);
     double dxh[SN], dnu[SE];

@@ -53,7 +53,10 @@ for k in order:
     prev = s[:, k]
 print("iteration 0 total            median %8.0f" % np.median(s[:, 8] - s[:, 6]))
 print("iter1 residuals+termination   median %8.0f" % np.median(s[:, 9] - s[:, 8]))
-it = [("residuals+resid", 9, None), ("factor_T", 10, 9), ("affine solve", 11, 10), ("corrector solve", 12, 11), ("xy + step", 13, 12)]
+# stamp 10 follows factor_T_rhs, which since the folded L sweep is the factorisation AND the whole affine solve; stamp 11
+# follows it at once in dqp_r16n.hip (interval ~0) and comes after the affine step length in dqp_r16.hip
+it = [("residuals+resid", 9, None), ("factor_T + affine solve", 10, 9), ("(r16: affine step length)", 11, 10),
+      ("corrector solve", 12, 11), ("xy + step", 13, 12)]
 for name, k, p in it[1:]:
     print("iter1 %-22s median %8.0f" % (name, np.median(s[:, k] - s[:, p])))
 print("loop total (all iterations)  median %8.0f  max %8.0f" % (np.median(s[:, 7] - s[:, 6]), (s[:, 7] - s[:, 6]).max()))
