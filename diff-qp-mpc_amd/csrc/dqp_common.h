@@ -94,8 +94,58 @@ __device__ __forceinline__ void term_zero_acc(const KParams &P)
     }
 }
 
+// the reference's rule on the batch-wide masks (dqp_term.hip) -> the iteration count it stops at
+__device__ __forceinline__ int rule_stop(unsigned long long ai, unsigned long long anb, unsigned long long ana, int maxIter,
+                                         int notImprovedLim)
+{
+    int nNot = 0;
+    for (int it = 0; it < maxIter; ++it) {
+        if (it == 0 || ((ai >> it) & 1ull)) nNot = 0;
+        else nNot += 1;
+        if (nNot == notImprovedLim || !((anb >> it) & 1ull) || !((ana >> it) & 1ull)) return it + 1;
+    }
+    return maxIter;
+}
+
+// a wave-uniform 64-bit value as scalar registers, whichever kind of load produced it
+__device__ __forceinline__ unsigned long long term_uniform(unsigned long long v)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// pass 2: the batch's stop I*.  A positive header was written by term_decide_kernel (multi-device form: the masks of
+// every shard combined).  0 -- pass 1 cleared it (term_zero_acc) and I* >= 1 -- means the scan left only the masks, which
+// sit in front of the header: the rule is replayed here, by every wavefront that needs I* (wave-uniform address and
+// result, the mask loads travel with the header's: the kernel boundary in front of pass 2 gives the visibility the
+// scan kernel used to buy with two device-wide fences).  The first lane of the grid leaves I* in the header for the caller.
+// Read it once per kernel: term_flagged and the iteration clamp take the value.
+// SCALAR (the null-space kernels, whose finish pass is on the path of every call): masks and rule in scalar registers.
+// Otherwise (the kernels that solve again in pass 2) the rule runs on vector registers: those kernels sit at the
+// register limit and pay for scalar pressure at their head with scratch (r16::forward_kernel at (30,30,15): 116 B in
+// front of this change, 176 B with the scalar form, 120 B with this one).
+template <bool SCALAR = false> __device__ __forceinline__ int term_cap(const KParams &P)
+{
+    const unsigned long long *m =
+        reinterpret_cast<const unsigned long long *>(reinterpret_cast<const char *>(P.cap) - (TERM_ACC_BYTES - TERM_HDR * 4));
+    const int c = P.cap[0];
+    // one memory round trip: left alone, the mask loads sink into the branch below and leave only after c has arrived
+    unsigned long long ai = m[0], anb = m[1], ana = m[2];
+    if (SCALAR) {
+        ai = term_uniform(ai); anb = term_uniform(anb); ana = term_uniform(ana);
+        asm volatile("" : "+s"(ai), "+s"(anb), "+s"(ana));
+    } else {
+        asm volatile("" : "+v"(ai), "+v"(anb), "+v"(ana));
+    }
+    if (c > 0) return c;
+    const int istar = rule_stop(ai, anb, ana, P.maxIter, P.notImprovedLim);
+    if (blockIdx.x == 0 && threadIdx.x == 0) const_cast<int32_t *>(P.cap)[0] = istar;
+    return istar;
+}
+
 // pass 2: a problem is taken back iff its best iterate of pass 1 came at an iteration the reference never ran
-__device__ __forceinline__ bool term_flagged(const KParams &P, long long qp) { return P.cap[TERM_HDR + qp] >= P.cap[0]; }
+__device__ __forceinline__ int term_best(const KParams &P, long long qp) { return P.cap[TERM_HDR + qp]; }
+__device__ __forceinline__ bool term_flagged(const KParams &P, long long qp, int cap) { return term_best(P, qp) >= cap; }
 
 // batch rule replay (dqp_term.hip); 0 on success
 size_t term_bytes(int B, int maxIter, int snapDim);

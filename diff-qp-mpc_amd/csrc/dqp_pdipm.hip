@@ -496,8 +496,9 @@ __global__ __launch_bounds__(WAVE) void qp_forward_kernel(KParams P)
     const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
     const bool strict = (P.flags & DQP_FLAG_STRICT_GET_STEP) != 0;
     if (P.cap) {        // pass 2 of the batch rule: only the listed QPs, up to the reference's stop
-        if (!term_flagged(P, qp)) return;
-        maxIter = min(maxIter, P.cap[0]);
+        const int cap = term_cap(P);
+        if (!term_flagged(P, qp, cap)) return;
+        maxIter = min(maxIter, cap);
     }
     const int status = qp_setup(P, S, qp, lane, rdq, rd1);
     const bool inN = lane < N, inM = lane < M, inE = lane < E;

@@ -276,8 +276,9 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
     const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
     const bool strict = (P.flags & DQP_FLAG_STRICT_GET_STEP) != 0;
     if (P.cap) {        // pass 2 of the batch rule: only the listed QPs, up to the reference's stop
-        maxIter = min(maxIter, P.cap[0]);
-        live = live && term_flagged(P, qp);
+        const int cap = term_cap(P);
+        maxIter = min(maxIter, cap);
+        live = live && term_flagged(P, qp, cap);
         if (__builtin_amdgcn_ballot_w64(live) == 0) return;
     }
     double *lds = sm + qrow * C::ldsQPpad;

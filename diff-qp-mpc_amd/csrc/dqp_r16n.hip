@@ -972,7 +972,8 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
 #pragma unroll
     for (int s = 0; s < SE; ++s) yv[s] = 0.0;
     if (E > 0) {
-        if (C::PARKWU) unpark_WU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
+        // (the finish pass has W and U from load_ctx)
+        if (C::PARKWU && reload_tails) unpark_WU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
         shift_up<C>(st.xy, xh, r);
         apply_Qf<C>(lds, st.tau, xh, r);
         double wz[SE];
@@ -1016,8 +1017,9 @@ __global__ __launch_bounds__(64) void forward_kernel(KParams P)
     const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
     const bool strict = (P.flags & DQP_FLAG_STRICT_GET_STEP) != 0;
     if (P.cap) {        // pass 2 of the batch rule: only the listed QPs, up to the reference's stop
-        maxIter = min(maxIter, P.cap[0]);
-        live = live && term_flagged(P, qp);
+        const int cap = term_cap<true>(P);
+        maxIter = min(maxIter, cap);
+        live = live && term_flagged(P, qp, cap);
         if (__builtin_amdgcn_ballot_w64(live) == 0) return;
     }
     double *lds = sm + qrow * C::ldsQPpad;
@@ -1286,9 +1288,11 @@ __global__ __launch_bounds__(64) void finish_kernel(KParams P)
     long long qp = (long long)blockIdx.x * 4 + qrow;
     bool live = qp < P.B;
     if (!live) qp = P.B - 1;
-    live = live && term_flagged(P, qp);
+    const int mine = term_best(P, qp);           // qp is clamped: no branch, in flight with the header and the masks
+    const int istar = term_cap<true>(P);
+    live = live && mine >= istar;
     if (__builtin_amdgcn_ballot_w64(live) == 0) return;
-    const int cap = min(P.maxIter, P.cap[0]);
+    const int cap = min(P.maxIter, istar);
     double *lds = sm + qrow * C::ldsQPpad;
     double *dummy = lds + C::oDummy + r;
     State<C> st;

@@ -13,7 +13,9 @@
 //
 // Buffer layout (dqp_termination_bytes): hist (maxIter, B) x {resid, mu} doubles | accumulators:
 // three u64 masks (improved, notbelow, notabove: one bit per iteration) | int32 header[TERM_HDR]
-// (header[0] = I*, header[2] = block arrival counter) then int32 best[B] (the iteration of each problem's
+// (header[0] = I*: written by the first lane of pass 2 -- the single-device scan leaves only the masks and every
+// pass-2 wavefront replays the rule on them, term_cap in dqp_common.h -- or, in the multi-device form, by
+// term_decide_kernel from the masks of all shards) then int32 best[B] (the iteration of each problem's
 // best iterate over all of pass 1: pass 2 takes a problem back iff best[qp] >= I*), then
 // (16-byte aligned) the iterate snapshots [maxIter][B][snapDim] of the null-space kernels: every
 // improving iterate of pass 1, so that pass 2 is an epilogue (r16n::finish_kernel), not a re-solve.
@@ -44,29 +46,15 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v)
     return v;
 }
 
-// the reference's rule on the batch-wide masks -> the iteration count it stops at
-__device__ __forceinline__ int rule_stop(unsigned long long ai, unsigned long long anb, unsigned long long ana, int maxIter,
-                                         int notImprovedLim)
-{
-    int nNot = 0;
-    for (int it = 0; it < maxIter; ++it) {
-        if (it == 0 || ((ai >> it) & 1ull)) nNot = 0;
-        else nNot += 1;
-        if (nNot == notImprovedLim || !((anb >> it) & 1ull) || !((ana >> it) & 1ull)) return it + 1;
-    }
-    return maxIter;
-}
-
 // One thread per problem walks its history (best-so-far, the iteration it was found at: stored in
 // hdr[TERM_HDR + qp], pass 2 compares it with I*) and collects its three masks; one OR-reduction per
-// wavefront, one atomicOr per block.  The last block to finish replays the reference's rule on the masks
-// and writes I* (hdr[0]; hdr[2] is the arrival counter).  The history is read SCAN_CHUNK iterations at a time
+// wavefront, one atomicOr per block.  The rule on the masks is replayed by the consumers (term_cap): a last-block
+// decision in here was two device-wide fences in series, most of this kernel's time.  The history is read SCAN_CHUNK iterations at a time
 // (independent loads: the default max_iter = 20 is one round trip), and nothing here is O(B) on one thread: the first version's last block turned the
 // best-iteration list into flags in a loop of dependent L2 round trips, two thirds of its 15 us.
 constexpr int SCAN_CHUNK = 32;
 __global__ __launch_bounds__(64) void term_scan_kernel(const double2 *hist, Acc *acc, int32_t *hdr,
-                                                       int B, int maxIter, int notImprovedLim, double eps,
-                                                       int decide)
+                                                       int B, int maxIter, double eps)
 {
     const int lane = threadIdx.x;
     const long long qp = (long long)blockIdx.x * blockDim.x + lane;
@@ -98,20 +86,6 @@ __global__ __launch_bounds__(64) void term_scan_kernel(const double2 *hist, Acc 
         const unsigned long long m = lane == 0 ? imp : (lane == 1 ? nb : na);
         unsigned long long *dst = lane == 0 ? &acc->improved : (lane == 1 ? &acc->notbelow : &acc->notabove);
         if (m) atomicOr(dst, m);
-    }
-    if (!decide) return;            // multi-device form: the masks are combined across devices first
-    // ---- last block: the rule itself
-    __threadfence();
-    int last = 0;
-    if (lane == 0) last = (atomicAdd(&hdr[2], 1) == (int)gridDim.x - 1);
-    last = __shfl(last, 0, 64);
-    if (!last) return;
-    __threadfence();
-    if (lane == 0) {
-        const unsigned long long ai = __hip_atomic_load(&acc->improved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long anb = __hip_atomic_load(&acc->notbelow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long ana = __hip_atomic_load(&acc->notabove, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        hdr[0] = rule_stop(ai, anb, ana, maxIter, notImprovedLim);
     }
 }
 
@@ -160,7 +134,7 @@ int term_decide(const KParams &P, void *term, void *stream)
     const int blocks = (P.B + 63) / 64;
     DQP_LAUNCH(term_scan_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream,
                        (const double2 *)term, acc_of(term, P.B, P.maxIter), hdr_of(term, P.B, P.maxIter),
-                       P.B, P.maxIter, P.notImprovedLim, P.eps, 1);
+                       P.B, P.maxIter, P.eps);
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
@@ -170,7 +144,7 @@ int term_local_masks(const KParams &P, void *term, unsigned long long *masks, vo
     const int blocks = (P.B + 63) / 64;
     DQP_LAUNCH(term_scan_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream,
                        (const double2 *)term, acc_of(term, P.B, P.maxIter), hdr_of(term, P.B, P.maxIter),
-                       P.B, P.maxIter, P.notImprovedLim, P.eps, 0);
+                       P.B, P.maxIter, P.eps);
     if (hipMemcpyAsync(masks, acc_of(term, P.B, P.maxIter), 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
                        (hipStream_t)stream) != hipSuccess)
         return DQP_ERR_LAUNCH;
