@@ -30,17 +30,25 @@ R16N_SIZES = [s for s in R16_SIZES if s[2] > 0] + [
     (35, 10, 30),   # n=6 m=1 T=5  (cartpole-2)
 ]
 
-# host-only stage-wise pairs (csrc/dqp_ric_host.hip; their union is DQP_RIC_HOST_SIZES of csrc/dqp_common.h), one
-# object per part: a wide pair alone takes ~30 s, so the parts compile side by side
+# Stage-wise (Riccati) MPC QP kernels: every compiled (n_state, n_ctrl) pair is named here and nowhere else.
+# csrc/dqp_ric.hip is compiled once per part of RIC_PARTS; csrc/dqp_ric_pad.hip gets the lists and the part names.
+# A kernel's machine code depends on which other pairs share its object, so moving a pair between parts changes it.
+RIC_SIZES = [(12, 4), (3, 3), (3, 1), (4, 1), (6, 1), (2, 1), (4, 2), (5, 1), (8, 1), (2, 2), (3, 2), (6, 2), (8, 2),
+             (6, 3), (4, 4), (8, 4), (10, 4), (12, 2)]      # n + m <= 16: four problems per wavefront
+RICW_SIZES = [(13, 4), (14, 7), (24, 8)]                    # 16 < n + m <= 32: two per wavefront
+# host-only pairs (they only run padded problems, dqp_mpc_dims.n_state_host), one object per part: a wide pair alone
+# takes ~30 s, so the parts compile side by side
 RIC_HOST_PARTS = [
     [(15, 1), (14, 2), (13, 3), (11, 5)], [(10, 6), (9, 7), (8, 8)],
     [(31, 1)], [(30, 2)], [(29, 3)], [(28, 4)], [(27, 5)], [(26, 6)], [(25, 7)],
 ]
+# (name, pairs); only "native" gets the LDS-resident and the registered-model variants, and the finish kernel
+RIC_PARTS = [("native", RIC_SIZES), ("wide", RICW_SIZES)] + [("host%d" % k, p) for k, p in enumerate(RIC_HOST_PARTS)]
 
-PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip", "dqp_al_banded.hip",
-                 "dqp_al_banded_wide.hip", "dqp_ric.hip", "dqp_ric_wide.hip", "dqp_ric_pad.hip", "dqp_trace.hip", "dqp_big.hip",
-                 "dqp_shared_grad.hip", "dqp_al_fused.hip"]
-SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric_host.hip"]
+PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_mpc_qp.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip",
+                 "dqp_al_banded.hip", "dqp_al_banded_wide.hip", "dqp_trace.hip", "dqp_big.hip", "dqp_shared_grad.hip",
+                 "dqp_al_fused.hip"]
+SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric.hip", "dqp_ric_pad.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-MD",
          "-mllvm", "-pragma-unroll-threshold=10000000", "-mllvm", "-unroll-threshold=10000000"]
 
@@ -81,18 +89,27 @@ def _jobs():
     for src in PLAIN_SOURCES:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         jobs.append((obj, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]))
-    for k, pairs in enumerate(RIC_HOST_PARTS):
-        obj = os.path.join(CSRC, "dqp_ric_host%d.o" % k)
-        jobs.append((obj, [cc] + FLAGS + ["-DDQP_RIC_HOST_PART=%d" % k,
-                                          "-DDQP_RIC_HOST_PART_SIZES=" + " ".join("X(%d,%d)" % p for p in pairs),
-                                          "-c", os.path.join(CSRC, "dqp_ric_host.hip"), "-o", obj]))
+    xs = lambda pairs: " ".join("X(%d,%d)" % p for p in pairs)
+    host = [p for part in RIC_HOST_PARTS for p in part]
+    # Cfg::INT_LDS of csrc/dqp_ric_kernels.h reads the 16-lane host pairs: the same list in every object
+    ric = FLAGS + ["-DDQP_RIC_HOST16_SIZES=" + xs([p for p in host if sum(p) <= 16])]
+    for name, pairs in RIC_PARTS:
+        obj = os.path.join(CSRC, "dqp_ric_%s.o" % name)
+        jobs.append((obj, [cc] + ric + ["-DDQP_RIC_PART=" + name, "-DDQP_RIC_PART_NATIVE=%d" % (name == "native"),
+                                        "-DDQP_RIC_PART_SIZES=" + xs(pairs),
+                                        "-c", os.path.join(CSRC, "dqp_ric.hip"), "-o", obj]))
+    obj = os.path.join(CSRC, "dqp_ric_pad.o")
+    jobs.append((obj, [cc] + ric + ["-DDQP_RIC_NATIVE_SIZES=" + xs(RIC_SIZES + RICW_SIZES),
+                                    "-DDQP_RIC_HOST_SIZES=" + xs(host),
+                                    "-DDQP_RIC_PARTS=" + " ".join("PART(%s)" % name for name, _ in RIC_PARTS),
+                                    "-c", os.path.join(CSRC, "dqp_ric_pad.hip"), "-o", obj]))
     # longest compiles first (the 3-slot null-space forwards take ~4 min each, the metric-size
     # kernels ~2-3 min, everything else seconds): keeps the wall time near total CPU / cores
     def cost(j):
         name = os.path.basename(j[0])
         m = [int(t) for t in name.replace(".o", "").split("_")[-3:]] if name.count("_") >= 4 else None
         if m is None:
-            if "ric" in name and "pad" not in name:            # stage-wise kernels: ~2 min (dqp_ric), ~30-50 s the others
+            if "ric" in name and "pad" not in name:            # stage-wise kernels: ~2 min (dqp_ric_native), ~30-50 s the others
                 return 10 ** 5
             if "banded_wide" in name:                          # three wide pairs in one object: ~6 min
                 return 10 ** 9

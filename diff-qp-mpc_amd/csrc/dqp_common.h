@@ -169,49 +169,29 @@ int r16_backward(const KParams &P, void *stream);
 int r16n_forward(const KParams &P, void *stream);
 long long r16n_workspace_doubles(int N, int M, int E);
 int r16n_snapshot_doubles(int N, int M, int E);
-// stage-wise (Riccati) PDIPM for MPC-structured QPs of any horizon (dqp_ric.hip): n + m <= 16
-bool ric_supported(int n_state, int n_ctrl);
-long long ric_workspace_doubles(int n_state, int n_ctrl, int T);
-int ric_forward(const KParams &P, void *stream);      // 1: no kernel for this (n, m)
-long long ric_stepped_workspace_doubles(int n_state, int n_ctrl, int T, int B);
-int ric_forward_stepped(const KParams &P, void *stream);   // iterations [P.itBegin, P.itEnd), residual from P.extRy
-int ric_backward(const KParams &P, void *stream);
-int ric_snapshot_doubles(int n_state, int n_ctrl, int T);   // iterate snapshot of the batch rule's finish pass
-int ric_finish(const KParams &P, void *stream);
-// the same kernels for 16 < n + m <= 32 (dqp_ric_wide.hip): one QP per 32-lane half-wavefront, the per-QP
-// workspace layout and the snapshot of the 16-lane form (ric_finish serves both), workspaces padded to an even B
-bool ricw_supported(int n_state, int n_ctrl);
-long long ricw_workspace_doubles(int n_state, int n_ctrl, int T);
-int ricw_forward(const KParams &P, void *stream);     // 1: no kernel for this (n, m) or a dynamics model
-long long ricw_stepped_workspace_doubles(int n_state, int n_ctrl, int T, int B);
-int ricw_forward_stepped(const KParams &P, void *stream);
-int ricw_backward(const KParams &P, void *stream);
-int ricw_snapshot_doubles(int n_state, int n_ctrl, int T);
-// host-only pairs of the same kernels (dqp_ric_host.hip, one object per part of _build.RIC_HOST_PARTS): no dense route
-// or native stage-wise route changes because of them, they only run padded problems (dqp_mpc_dims.n_state_host)
-#define DQP_RIC_HOST16_SIZES X(15, 1) X(14, 2) X(13, 3) X(11, 5) X(10, 6) X(9, 7) X(8, 8)
-#define DQP_RIC_HOSTW_SIZES X(31, 1) X(30, 2) X(29, 3) X(28, 4) X(27, 5) X(26, 6) X(25, 7)
-#define DQP_RIC_HOST_SIZES DQP_RIC_HOST16_SIZES DQP_RIC_HOSTW_SIZES
-#define DQP_RIC_HOST_PART_IDS PART(0) PART(1) PART(2) PART(3) PART(4) PART(5) PART(6) PART(7) PART(8)
-enum { RIC_HOST_FORWARD = 0, RIC_HOST_STEPPED = 1, RIC_HOST_BACKWARD = 2 };
-#define PART(k) int ric_host_run_##k(int op, const KParams &P, void *stream);    // 1: not a pair of part k
-DQP_RIC_HOST_PART_IDS
-#undef PART
-// any stage-wise pair, native or host-only (dqp_ric_pad.hip): the same per-QP layout and snapshot in all families
+// stage-wise (Riccati) PDIPM for MPC-structured QPs of any horizon (kernels: dqp_ric_kernels.h), one interface for every
+// compiled (n_state, n_ctrl) pair (dqp_ric_pad.hip).  The pairs are _build.py's: native (a problem of that size runs on
+// them as it is) or host-only (they only run padded problems, dqp_mpc_dims.n_state_host); the per-QP workspace layout and
+// the snapshot of the batch rule's finish pass are the same in all of them.
 bool stage_supported(int n_state, int n_ctrl);
-bool stage_native(int n_state, int n_ctrl);                     // ric_supported || ricw_supported
+bool stage_native(int n_state, int n_ctrl);
 int stage_q(int n_state, int n_ctrl);                           // problems per wavefront: 4 (n + m <= 16) or 2
-long long stage_layout_doubles(int n_state, int n_ctrl, int T); // 0: no kernel for (n, m)
-int stage_forward(const KParams &P, void *stream);              // the linear-residual forward (no registered model)
-int stage_forward_stepped(const KParams &P, void *stream);
+long long stage_layout_doubles(int n_state, int n_ctrl, int T); // per QP; 0: no kernel for (n, m)
+int stage_snapshot_doubles(int n_state, int n_ctrl, int T);
+// B rounded up to whole wavefronts (padding rows own a slot too) times the layout; stepped: plus the loop state per slot
+long long stage_workspace_doubles(int n_state, int n_ctrl, int T, int B, bool stepped);
+// 1: no kernel for this (n, m), or for P.dynId on it (only native 16-lane pairs have registered models)
+int stage_forward(const KParams &P, void *stream);
+int stage_forward_stepped(const KParams &P, void *stream);      // iterations [P.itBegin, P.itEnd), residual from P.extRy
 int stage_backward(const KParams &P, void *stream);
+int stage_finish(const KParams &P, void *stream);               // dqp_ric.hip, the native part
+enum { STAGE_FORWARD = 0, STAGE_STEPPED = 1, STAGE_BACKWARD = 2 };   // op of a part's stage_run_<part>(op, P, stream)
 // Padded problems: a problem (n, m) on the kernels of (n', m), n' >= n, with n' - n dummy states after the real ones
-// (identity cost, zero dynamics rows, zero start).  Region of the caller's workspace behind the kernels' part:
+// (identity cost, zero dynamics rows, zero start).  Region of the caller's workspace behind the kernels' part
+// (stage_workspace_doubles of the host pair):
 struct PadRegion {
     double *C, *F, *c, *tau, *g, *dc, *f, *df, *nu, *ry, *x0, *dx0, *dC, *dF;
 };
-// the kernels' part in front of it: B rounded up to whole wavefronts times the per-QP workspace (stepped: plus the loop state)
-long long pad_kernel_doubles(int n_host, int n_ctrl, int T, int B, bool stepped);
 long long pad_region_doubles(int n_host, int n_ctrl, int T, int B);
 PadRegion pad_region(double *base, int n_host, int n_ctrl, int T, int B);
 // the copies (element-wise, coalesced, no host synchronisation); NULL arrays are skipped
@@ -233,6 +213,10 @@ int al_banded_newton_step_keep(const dqp_al_mpc_dims *d, int dyn_id, double dt, 
                                void *stream, int keep);
 // backward restarted from the context r16n_forward left in P.workspace (DQP_FLAG_BACKWARD_CTX)
 int r16n_backward(const KParams &P, void *stream);
+
+// dqp_pdipm.hip: the parameter block of a dense QP call (sizes, strides, options; lds_bytes: what the generic kernels need)
+void fill_opts(const dqp_opts *o, KParams &P);
+int fill_params(const dqp_dims *d, const dqp_opts *o, KParams &P, size_t &lds_bytes);
 
 }  // namespace dqp
 #endif

@@ -677,7 +677,25 @@ __global__ __launch_bounds__(WAVE) void qp_backward_kernel(KParams P)
     if (lane == 0 && P.info) { P.info[2 * qp] = status; P.info[2 * qp + 1] = 0; }
 }
 
+template <typename K>
+int launch(K kernel, const KParams &P, size_t lds_bytes, void *stream)
+{
+    if (P.B == 0) return DQP_OK;
+    if (lds_bytes > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_bytes) != hipSuccess)
+            return DQP_ERR_LAUNCH;
+    }
+    DQP_LAUNCH(kernel, dim3(P.B), dim3(WAVE), lds_bytes, (hipStream_t)stream, P);
+    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+}
+
+}  // namespace
+
 static inline bool is_big(const KParams &P) { return P.N > DQP_MAX_DIM || P.M > DQP_MAX_DIM || P.E > DQP_MAX_DIM; }
+
+namespace dqp {
 
 void fill_opts(const dqp_opts *o, KParams &P)
 {
@@ -743,21 +761,7 @@ int fill_params(const dqp_dims *d, const dqp_opts *o, KParams &P, size_t &lds_by
     return DQP_OK;
 }
 
-template <typename K>
-int launch(K kernel, const KParams &P, size_t lds_bytes, void *stream)
-{
-    if (P.B == 0) return DQP_OK;
-    if (lds_bytes > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes) != hipSuccess)
-            return DQP_ERR_LAUNCH;
-    }
-    DQP_LAUNCH(kernel, dim3(P.B), dim3(WAVE), lds_bytes, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-}
-
-}  // namespace
+}  // namespace dqp
 
 #ifdef DQP_STAMPS
 namespace dqp { unsigned long long *g_debug_stamps = nullptr; }
@@ -808,6 +812,20 @@ dqp_termination_bytes(const dqp_dims *d, const dqp_opts *o)
 
 static int forward_once(const KParams &P, size_t lds, void *workspace, void *stream);
 
+// the arrays of a dense forward call (dqp_qp_forward, dqp_qp_forward_finish)
+static int bind_forward(KParams &P, const double *Q, const double *p, const double *G, const double *h, const double *A,
+                        const double *b, double *zhat, double *lam, double *nu, double *slack, int32_t *info,
+                        double *best_resid, void *workspace)
+{
+    if (!Q || !p || !G || !h || !zhat || !lam || !slack) return DQP_ERR_BAD_ARG;
+    if (P.E > 0 && (!A || !b || !nu)) return DQP_ERR_BAD_ARG;
+    P.Q = Q; P.p = p; P.G = G; P.h = h; P.A = A; P.b = b;
+    P.zhat = zhat; P.lam = lam; P.nu = nu; P.slack = slack;
+    P.info = info; P.best_resid = best_resid;
+    P.workspace = (double *)workspace;
+    return DQP_OK;
+}
+
 __attribute__((visibility("default"))) int
 dqp_qp_forward(const dqp_dims *dims, const dqp_opts *opts, const double *Q, const double *p,
                const double *G, const double *h, const double *A, const double *b, double *zhat,
@@ -819,12 +837,7 @@ dqp_qp_forward(const dqp_dims *dims, const dqp_opts *opts, const double *Q, cons
     int rc = fill_params(dims, opts, P, lds);
     if (rc != DQP_OK) return rc;
     if (P.B == 0) return DQP_OK;
-    if (!Q || !p || !G || !h || !zhat || !lam || !slack) return DQP_ERR_BAD_ARG;
-    P.workspace = (double *)workspace;
-    if (P.E > 0 && (!A || !b || !nu)) return DQP_ERR_BAD_ARG;
-    P.Q = Q; P.p = p; P.G = G; P.h = h; P.A = A; P.b = b;
-    P.zhat = zhat; P.lam = lam; P.nu = nu; P.slack = slack;
-    P.info = info; P.best_resid = best_resid;
+    if ((rc = bind_forward(P, Q, p, G, h, A, b, zhat, lam, nu, slack, info, best_resid, workspace)) != DQP_OK) return rc;
     if (!(P.flags & DQP_FLAG_BATCH_TERMINATION)) return forward_once(P, lds, workspace, stream);
     // The reference's batch-coupled stop (batch.py:119-144), replayed on the device:
     //   1. every problem iterates to max_iter, recording (resid, mu) per iteration;
@@ -872,12 +885,7 @@ dqp_qp_forward_finish(const dqp_dims *dims, const dqp_opts *opts, const double *
     if (P.B == 0) return DQP_OK;
     if (!(P.flags & DQP_FLAG_BATCH_TERMINATION) || !termination || !masks || P.maxIter < 1 || P.maxIter > 64)
         return DQP_ERR_BAD_ARG;
-    if (!Q || !p || !G || !h || !zhat || !lam || !slack) return DQP_ERR_BAD_ARG;
-    if (P.E > 0 && (!A || !b || !nu)) return DQP_ERR_BAD_ARG;
-    P.workspace = (double *)workspace;
-    P.Q = Q; P.p = p; P.G = G; P.h = h; P.A = A; P.b = b;
-    P.zhat = zhat; P.lam = lam; P.nu = nu; P.slack = slack;
-    P.info = info; P.best_resid = best_resid;
+    if ((rc = bind_forward(P, Q, p, G, h, A, b, zhat, lam, nu, slack, info, best_resid, workspace)) != DQP_OK) return rc;
     P.eps = opts ? opts->eps : 1e-12;
     const bool nullspace = workspace && !(P.flags & (DQP_FLAG_GENERIC_ONLY | DQP_FLAG_NO_NULLSPACE)) && !P.dynId && !is_big(P);
     term_bind_pass1(P, termination, nullspace ? r16n_snapshot_doubles(P.N, P.M, P.E) : 0);    // (snapshot pointer)
@@ -901,328 +909,6 @@ static int forward_once(const KParams &P, size_t lds, void *workspace, void *str
     if (mx <= 16) return launch(qp_forward_kernel<16>, P, lds, stream);
     if (mx <= 32) return launch(qp_forward_kernel<32>, P, lds, stream);
     return launch(qp_forward_kernel<64>, P, lds, stream);
-}
-
-// MPC-structured entry points: the null-space kernels assemble (Q,p,G,h,A,b) in registers from the
-// time-major MPC data and scatter the gradients back the same way -- no dense QP in HBM.
-// Which kernels serve an MPC shape: the dense null-space kernels where the QP size has an
-// instantiation (small horizons: one QP in registers), else the stage-wise Riccati kernels
-// (dqp_ric.hip: any horizon, n + m <= 16; dqp_ric_wide.hip: the same for 16 < n + m <= 32).  MPC_PAD: the caller
-// names a host pair (dqp_mpc_dims.n_state_host), the problem runs padded with dummy states on its stage-wise kernels
-// (dqp_ric_pad.hip; the padded copies live in the caller's workspace behind the kernels' part).
-enum { MPC_NONE = 0, MPC_R16N = 1, MPC_RIC = 2, MPC_RICW = 3, MPC_PAD = 4 };
-
-// per-QP workspace of the stage-wise kernels (the same layout in both families); 0: no kernel for (n, m)
-static long long stage_ws_doubles(int n, int m, int T)
-{
-    return ric_supported(n, m) ? ric_workspace_doubles(n, m, T) : ricw_workspace_doubles(n, m, T);
-}
-
-static int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, size_t &lds, int &kind)
-{
-    kind = MPC_NONE;
-    if (!md || md->T < 2 || md->n_state < 1 || md->n_ctrl < 1 || !md->has_bounds || md->nbatch < 0) return DQP_ERR_BAD_ARG;
-    dqp_dims d = {};
-    d.nbatch = md->nbatch;
-    d.nz = md->T * (md->n_state + md->n_ctrl);
-    d.nineq = 2 * md->T * md->n_ctrl;
-    d.neq = md->T * md->n_state;
-    if (md->n_state_host) {     // a host pair: every registered model is native, no null-space route
-        const int np = md->n_state_host, m = md->n_ctrl;
-        if (md->dyn_id || np < md->n_state || !stage_supported(np, m)) return DQP_ERR_BAD_ARG;
-        if (md->T > 200000 || stage_layout_doubles(np, m, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
-        P.stamps = nullptr;
-        P.B = d.nbatch; P.N = md->T * (np + m); P.M = d.nineq; P.E = md->T * np;
-        fill_opts(opts, P);
-        P.dynId = 0; P.dynDt = 0.0;
-        P.mn = np; P.mm = m; P.mT = md->T;
-        kind = MPC_PAD;
-        return DQP_OK;
-    }
-    if (md->dyn_id) {       // true-dynamics residual: a registered model of this size, stage-wise kernels
-        int32_t dn = 0, dm = 0;
-        if (dqp_dyn_sizes(md->dyn_id, &dn, &dm) != DQP_OK || dn != md->n_state || dm != md->n_ctrl) return DQP_ERR_BAD_ARG;
-    }
-    const bool stagewise = opts && (opts->flags & DQP_FLAG_STAGEWISE);
-    if (!md->dyn_id && !stagewise && r16n_workspace_doubles(d.nz, d.nineq, d.neq) > 0) {
-        dqp_opts o2;
-        if (opts) { o2 = *opts; o2.dyn_id = 0; }
-        int rc = fill_params(&d, opts ? &o2 : nullptr, P, lds);
-        if (rc != DQP_OK) return rc;
-        kind = MPC_R16N;
-    } else if (ric_supported(md->n_state, md->n_ctrl) || ricw_supported(md->n_state, md->n_ctrl)) {
-        // the stage-wise kernels address a wavefront's four workspaces with 32-bit byte offsets
-        if (md->T > 200000 || stage_ws_doubles(md->n_state, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
-        P.stamps = nullptr;
-        P.B = d.nbatch; P.N = d.nz; P.M = d.nineq; P.E = d.neq;
-        fill_opts(opts, P);
-        P.dynId = md->dyn_id;
-        P.dynDt = opts ? opts->dyn_dt : 0.0;
-        kind = ric_supported(md->n_state, md->n_ctrl) ? MPC_RIC : MPC_RICW;
-    } else {
-        return DQP_ERR_TOO_LARGE;
-    }
-    P.mn = md->n_state; P.mm = md->n_ctrl; P.mT = md->T;
-    return DQP_OK;
-}
-
-static size_t mpc_workspace_doubles(const KParams &P, int kind)
-{
-    if (kind == MPC_PAD) return (size_t)(pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false) + pad_region_doubles(P.mn, P.mm, P.mT, P.B));
-    if (kind == MPC_R16N) return (size_t)P.B * (size_t)r16n_workspace_doubles(P.N, P.M, P.E);
-    // four problems per wavefront (two for the wide pairs), padding rows own a slot too
-    if (kind == MPC_RICW) return (size_t)((P.B + 1) / 2 * 2) * (size_t)ricw_workspace_doubles(P.mn, P.mm, P.mT);
-    return (size_t)((P.B + 3) / 4 * 4) * (size_t)ric_workspace_doubles(P.mn, P.mm, P.mT);
-}
-
-static int mpc_snapshot_doubles(const KParams &P, int kind)
-{
-    if (kind == MPC_PAD) return P.mT * (2 * P.mn + 5 * P.mm);      // the stage-wise snapshot of the host pair
-    if (kind == MPC_RICW) return ricw_snapshot_doubles(P.mn, P.mm, P.mT);
-    return kind == MPC_R16N ? r16n_snapshot_doubles(P.N, P.M, P.E) : ric_snapshot_doubles(P.mn, P.mm, P.mT);
-}
-
-__attribute__((visibility("default"))) size_t dqp_mpc_qp_termination_bytes(const dqp_mpc_dims *md, const dqp_opts *o)
-{
-    KParams P = {};
-    size_t lds = 0;
-    int kind;
-    if (!o || !(o->flags & DQP_FLAG_BATCH_TERMINATION) || mpc_params(md, o, P, lds, kind) != DQP_OK || md->nbatch <= 0) return 0;
-    return term_bytes(P.B, P.maxIter, mpc_snapshot_doubles(P, kind));
-}
-
-__attribute__((visibility("default"))) int dqp_mpc_qp_supported(const dqp_mpc_dims *md)
-{
-    KParams P = {};
-    size_t lds = 0;
-    int kind;
-    return mpc_params(md, nullptr, P, lds, kind) == DQP_OK ? 1 : 0;
-}
-
-__attribute__((visibility("default"))) size_t dqp_mpc_qp_workspace_bytes(const dqp_mpc_dims *md)
-{
-    KParams P = {};
-    size_t lds = 0;
-    int kind;
-    if (mpc_params(md, nullptr, P, lds, kind) != DQP_OK || md->nbatch <= 0) return 0;
-    return mpc_workspace_doubles(P, kind) * sizeof(double);
-}
-
-__attribute__((visibility("default"))) int
-dqp_mpc_qp_forward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
-                   const double *F, const double *f, const double *x0, const double *u_lower,
-                   const double *u_upper, double *tau, double *lam, double *nu, double *slack,
-                   int32_t *info, double *best_resid, void *workspace, void *termination, void *stream)
-{
-    const dqp_mpc_bounds bounds = {u_lower, u_upper, 0, 0};
-    return dqp_mpc_qp_forward_bounds(md, opts, C, c, F, f, x0, &bounds, tau, lam, nu, slack, info, best_resid, workspace,
-                                     termination, stream);
-}
-
-// the bounds of sample b, knot t, control k at [b stride_b + t stride_t + k] (include/dqp.h: dqp_mpc_bounds).  The padded
-// route passes them through as they are: controls are not padded.
-__attribute__((visibility("default"))) int
-dqp_mpc_qp_forward_bounds(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
-                          const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
-                          double *tau, double *lam, double *nu, double *slack, int32_t *info, double *best_resid,
-                          void *workspace, void *termination, void *stream)
-{
-    KParams P = {};
-    size_t lds = 0;
-    int kind;
-    int rc = mpc_params(md, opts, P, lds, kind);
-    if (rc != DQP_OK) return rc;
-    if ((rc = mpc_bounds_layout(bounds, md)) != DQP_OK) return rc;
-    if (P.B == 0) return DQP_OK;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    if (!C || !c || !F || !f || !x0 || !u_lower || !u_upper || !tau || !lam || !nu || !slack || !workspace)
-        return DQP_ERR_BAD_ARG;
-    if (P.dynId && !(P.dynDt > 0.0)) return DQP_ERR_BAD_ARG;        // the model's step needs dqp_opts.dyn_dt
-    auto run = [&](const KParams &Q) {
-        if (kind == MPC_PAD) return stage_forward(Q, stream);
-        return kind == MPC_R16N ? r16n_forward(Q, stream) : kind == MPC_RICW ? ricw_forward(Q, stream) : ric_forward(Q, stream);
-    };
-    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0;
-    mpc_set_bounds(P, bounds);
-    P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
-    P.workspace = (double *)workspace;
-    if (P.maxIter < 1) return DQP_ERR_BAD_ARG;
-    const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
-    if (batch && (!termination || P.maxIter > 64)) return DQP_ERR_BAD_ARG;
-    // padded: the host kernels read the padded copies and write tau, nu padded (lam, slack have the caller's layout)
-    PadRegion R = {};
-    if (kind == MPC_PAD) {
-        R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false), P.mn, P.mm, P.mT, P.B);
-        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, C, c, F, f, x0, nullptr, nullptr, nullptr, nullptr, stream);
-        if (rc != DQP_OK) return rc;
-        P.mC = R.C; P.mc = R.c; P.mF = R.F; P.mf = R.f; P.mx0 = R.x0; P.zhat = R.tau; P.nu = R.nu;
-    }
-    auto done = [&](int r) {
-        if (r != DQP_OK || kind != MPC_PAD) return r;
-        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, tau, nu, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-    };
-    if (!batch) return done(run(P));
-    P.eps = opts ? opts->eps : 1e-12;
-    term_bind_pass1(P, termination, mpc_snapshot_doubles(P, kind));
-    if ((rc = run(P)) != DQP_OK) return rc;
-    if (P.flags & DQP_FLAG_HISTORY_ONLY) return done(DQP_OK);
-    if ((rc = term_decide(P, termination, stream)) != DQP_OK) return rc;
-    term_bind_pass2(P, termination);
-    return done(kind == MPC_R16N ? r16n_forward(P, stream) : ric_finish(P, stream));
-}
-
-static int stage_snapshot_doubles(int n, int m, int T)
-{
-    return stage_supported(n, m) ? T * (2 * n + 5 * m) : 0;        // ric_snapshot_doubles of every stage-wise pair
-}
-
-// the stage-wise kernels only, whatever the horizon (the null-space kernels keep their iterate in registers); with
-// n_state_host the kernels of (n_state_host, n_ctrl) on the padded problem (P.mn is then the host's state count)
-static int stepped_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P)
-{
-    if (!md || md->nbatch < 0 || md->n_state <= 0 || md->n_ctrl <= 0 || md->T < 2 || !md->has_bounds) return DQP_ERR_BAD_ARG;
-    int np = md->n_state;
-    if (md->n_state_host) {
-        np = md->n_state_host;
-        if (md->dyn_id || np < md->n_state || !stage_supported(np, md->n_ctrl)) return DQP_ERR_BAD_ARG;
-    } else if (!ric_supported(md->n_state, md->n_ctrl) && !ricw_supported(md->n_state, md->n_ctrl)) {
-        return DQP_ERR_TOO_LARGE;
-    }
-    if (md->T > 200000 || stage_layout_doubles(np, md->n_ctrl, md->T) * 8 * 4 > 0x7fffffffLL) return DQP_ERR_TOO_LARGE;
-    P.B = md->nbatch;
-    P.N = md->T * (np + md->n_ctrl); P.M = 2 * md->T * md->n_ctrl; P.E = md->T * np;
-    fill_opts(opts, P);
-    P.mn = np; P.mm = md->n_ctrl; P.mT = md->T;
-    return DQP_OK;
-}
-
-__attribute__((visibility("default"))) size_t dqp_mpc_qp_stepped_workspace_bytes(const dqp_mpc_dims *md)
-{
-    KParams P = {};
-    if (stepped_params(md, nullptr, P) != DQP_OK || md->nbatch <= 0) return 0;
-    if (md->n_state_host)
-        return (size_t)(pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, true) + pad_region_doubles(P.mn, P.mm, P.mT, P.B)) * sizeof(double);
-    const long long n = ric_supported(P.mn, P.mm) ? ric_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B)
-                                                  : ricw_stepped_workspace_doubles(P.mn, P.mm, P.mT, P.B);
-    return (size_t)n * sizeof(double);
-}
-
-__attribute__((visibility("default"))) size_t dqp_mpc_qp_stepped_termination_bytes(const dqp_mpc_dims *md, const dqp_opts *o)
-{
-    KParams P = {};
-    if (!o || !(o->flags & DQP_FLAG_BATCH_TERMINATION) || stepped_params(md, o, P) != DQP_OK || md->nbatch <= 0) return 0;
-    return term_bytes(P.B, P.maxIter, stage_snapshot_doubles(P.mn, P.mm, P.mT));
-}
-
-__attribute__((visibility("default"))) int
-dqp_mpc_qp_forward_stepped(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
-                           const double *F, const double *f, const double *x0, const double *u_lower,
-                           const double *u_upper, const double *ext_ry, int32_t it_begin, int32_t it_end,
-                           double *tau, double *lam, double *nu, double *slack, int32_t *info, double *best_resid,
-                           void *workspace, void *termination, void *stream)
-{
-    const dqp_mpc_bounds bounds = {u_lower, u_upper, 0, 0};
-    return dqp_mpc_qp_forward_stepped_bounds(md, opts, C, c, F, f, x0, &bounds, ext_ry, it_begin, it_end, tau, lam, nu, slack,
-                                             info, best_resid, workspace, termination, stream);
-}
-
-__attribute__((visibility("default"))) int
-dqp_mpc_qp_forward_stepped_bounds(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *c,
-                                  const double *F, const double *f, const double *x0, const dqp_mpc_bounds *bounds,
-                                  const double *ext_ry, int32_t it_begin, int32_t it_end, double *tau, double *lam,
-                                  double *nu, double *slack, int32_t *info, double *best_resid, void *workspace,
-                                  void *termination, void *stream)
-{
-    KParams P = {};
-    int rc = stepped_params(md, opts, P);
-    if (rc != DQP_OK) return rc;
-    if ((rc = mpc_bounds_layout(bounds, md)) != DQP_OK) return rc;
-    if (P.B == 0) return DQP_OK;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    if (!C || !c || !F || !f || !x0 || !u_lower || !u_upper || !tau || !lam || !nu || !slack || !workspace)
-        return DQP_ERR_BAD_ARG;
-    if (P.maxIter < 1 || it_begin < 0 || it_end < it_begin || it_end > P.maxIter || it_end - it_begin > 1) return DQP_ERR_BAD_ARG;
-    if (it_end > it_begin && !ext_ry) return DQP_ERR_BAD_ARG;
-    if (it_end == it_begin && it_begin != 0) return DQP_ERR_BAD_ARG;
-    P.mC = C; P.mc = c; P.mF = F; P.mf = f; P.mx0 = x0;
-    mpc_set_bounds(P, bounds);
-    P.zhat = tau; P.lam = lam; P.nu = nu; P.slack = slack; P.info = info; P.best_resid = best_resid;
-    P.workspace = (double *)workspace;
-    P.extRy = ext_ry; P.itBegin = it_begin; P.itEnd = it_end;
-    const bool batch = (P.flags & DQP_FLAG_BATCH_TERMINATION) != 0;
-    if (batch && (!termination || P.maxIter > 64)) return DQP_ERR_BAD_ARG;
-    // padded: the call that starts the solve packs the problem, the later ones reuse that copy; every call pads
-    // ext_ry and hands the caller the compact iterate (and the compact nu with the final one)
-    const bool pad = md->n_state_host != 0;
-    PadRegion R = {};
-    if (pad) {
-        R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, true), P.mn, P.mm, P.mT, P.B);
-        const bool first = it_begin == 0;
-        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, first ? C : nullptr, first ? c : nullptr, first ? F : nullptr,
-                      first ? f : nullptr, first ? x0 : nullptr, nullptr, nullptr, nullptr, it_end > it_begin ? ext_ry : nullptr,
-                      stream);
-        if (rc != DQP_OK) return rc;
-        P.mC = R.C; P.mc = R.c; P.mF = R.F; P.mf = R.f; P.mx0 = R.x0; P.zhat = R.tau; P.nu = R.nu;
-        P.extRy = it_end > it_begin ? R.ry : nullptr;
-    }
-    auto done = [&](int r) {
-        if (r != DQP_OK || !pad) return r;
-        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, tau, it_end == P.maxIter ? nu : nullptr, nullptr, nullptr,
-                          nullptr, nullptr, nullptr, stream);
-    };
-    if (batch) {
-        P.eps = opts ? opts->eps : 1e-12;
-        term_bind_pass1(P, termination, stage_snapshot_doubles(P.mn, P.mm, P.mT));
-    }
-    rc = pad ? stage_forward_stepped(P, stream) : ric_supported(P.mn, P.mm) ? ric_forward_stepped(P, stream) : ricw_forward_stepped(P, stream);
-    if (rc != DQP_OK) return rc == 1 ? DQP_ERR_TOO_LARGE : rc;
-    if (it_end < P.maxIter || !batch || (P.flags & DQP_FLAG_HISTORY_ONLY)) return done(DQP_OK);
-    if ((rc = term_decide(P, termination, stream)) != DQP_OK) return rc;
-    term_bind_pass2(P, termination);
-    return done(ric_finish(P, stream));
-}
-
-__attribute__((visibility("default"))) int
-dqp_mpc_qp_backward(const dqp_mpc_dims *md, const dqp_opts *opts, const double *C, const double *F,
-                    const double *tau, const double *lam, const double *nu, const double *slack,
-                    const double *dl_dtau, double *dC, double *dc, double *dF, double *df, double *dx0,
-                    int32_t *info, void *workspace, void *stream)
-{
-    KParams P = {};
-    size_t lds = 0;
-    int kind;
-    int rc = mpc_params(md, opts, P, lds, kind);
-    if (rc != DQP_OK) return rc;
-    if (P.B == 0) return DQP_OK;
-    if (!tau || !lam || !nu || !slack || !dl_dtau || !workspace) return DQP_ERR_BAD_ARG;
-    if (!dC && !dc && !dF && !df && !dx0) return DQP_OK;
-    P.zin = tau; P.lamin = lam; P.nuin = nu; P.slackin = slack; P.gin = dl_dtau;
-    P.mdC = dC; P.mdc = dc; P.mdF = dF; P.mdf = df; P.mdx0 = dx0;
-    P.info = info;
-    P.workspace = (double *)workspace;
-    if (kind == MPC_R16N) return r16n_backward(P, stream);
-    if (!C || !F) return DQP_ERR_BAD_ARG;
-    P.mC = C; P.mF = F;
-    if (kind == MPC_PAD) {      // re-padded inputs (their dummy entries are exactly zero), padded gradients, compact copies
-        const PadRegion R = pad_region(P.workspace + pad_kernel_doubles(P.mn, P.mm, P.mT, P.B, false), P.mn, P.mm, P.mT, P.B);
-        rc = pad_pack(md->n_state, P.mn, P.mm, P.mT, P.B, R, C, nullptr, F, nullptr, nullptr, tau, nu, dl_dtau, nullptr, stream);
-        if (rc != DQP_OK) return rc;
-        P.mC = R.C; P.mF = R.F; P.zin = R.tau; P.nuin = R.nu; P.gin = R.g;
-        P.mdC = dC ? R.dC : nullptr; P.mdc = dc ? R.dc : nullptr; P.mdF = dF ? R.dF : nullptr;
-        P.mdf = df ? R.df : nullptr; P.mdx0 = dx0 ? R.dx0 : nullptr;
-        if ((rc = stage_backward(P, stream)) != DQP_OK) return rc;
-        return pad_unpack(md->n_state, P.mn, P.mm, P.mT, P.B, R, nullptr, nullptr, dC, dc, dF, df, dx0, stream);
-    }
-    return kind == MPC_RICW ? ricw_backward(P, stream) : ric_backward(P, stream);
-}
-
-// the smallest compiled stage-wise pair (n', n_ctrl), n' >= n_state, native or host-only; 0: none
-__attribute__((visibility("default"))) int32_t dqp_mpc_qp_host_n_state(const dqp_mpc_dims *md)
-{
-    if (!md || md->n_state < 1 || md->n_ctrl < 1 || !md->has_bounds || md->dyn_id) return 0;
-    for (int np = md->n_state; np + md->n_ctrl <= 32; ++np)     // ascending n': the 16-lane pairs come first
-        if (stage_supported(np, md->n_ctrl)) return np;
-    return 0;
 }
 
 __attribute__((visibility("default"))) int

@@ -8,55 +8,47 @@
 // iterates, directions and costates stay exactly zero and the residuals, mu, the step lengths and the batch rule
 // are those of the (n, m) problem.  The results equal the native ones up to the association of the lane reductions.
 //
-// This file: which pairs exist (native or host-only), the layout of the padded copies in the caller's workspace
-// and the pack / unpack copies into and out of it.
-#define DQP_RIC_KERNELS_ONLY
-#include "dqp_ric.hip"
+// This file: the one interface to the stage-wise kernels (dqp_common.h: stage_*) -- which pairs exist, native or
+// host-only, their sizes, and the dispatch over the parts of dqp_ric.hip -- then the layout of the padded copies in the
+// caller's workspace and the pack / unpack copies into and out of it.  The pairs and the parts come from _build.py.
+#include "dqp_ric_kernels.h"
+
+#if !defined(DQP_RIC_NATIVE_SIZES) || !defined(DQP_RIC_HOST_SIZES) || !defined(DQP_RIC_PARTS)
+#error "compile with -DDQP_RIC_NATIVE_SIZES / -DDQP_RIC_HOST_SIZES=\"X(n, m) ...\" and -DDQP_RIC_PARTS=\"PART(name) ...\""
+#endif
 
 namespace dqp {
 
-static bool ric_host_supported(int n, int m)
-{
-#define X(a, b) if (n == a && m == b) return true;
-    DQP_RIC_HOST_SIZES
+#define X(a, b) (n == a && m == b) ||
+bool stage_native(int n, int m) { return DQP_RIC_NATIVE_SIZES false; }
+bool stage_supported(int n, int m) { return DQP_RIC_NATIVE_SIZES DQP_RIC_HOST_SIZES false; }
 #undef X
-    return false;
-}
-
-bool stage_native(int n, int m) { return ric_supported(n, m) || ricw_supported(n, m); }
-bool stage_supported(int n, int m) { return stage_native(n, m) || ric_host_supported(n, m); }
 int stage_q(int n, int m) { return n + m <= 16 ? 4 : 2; }
 long long stage_layout_doubles(int n, int m, int T) { return stage_supported(n, m) ? ric::layout(n, m, T).total : 0; }
+int stage_snapshot_doubles(int n, int m, int T) { return stage_supported(n, m) ? T * (2 * n + 5 * m) : 0; }
 
-static int ric_host_run(int op, const KParams &P, void *stream)
+long long stage_workspace_doubles(int n, int m, int T, int B, bool stepped)
+{
+    const int q = stage_q(n, m);
+    return (long long)((B + q - 1) / q * q) * (stage_layout_doubles(n, m, T) + (stepped ? ric::STEP_STATE : 0));
+}
+
+#define PART(name) int stage_run_##name(int op, const KParams &P, void *stream);
+DQP_RIC_PARTS
+#undef PART
+
+static int stage_run(int op, const KParams &P, void *stream)
 {
     int rc;
-#define PART(k) if ((rc = ric_host_run_##k(op, P, stream)) != 1) return rc;
-    DQP_RIC_HOST_PART_IDS
+#define PART(name) if ((rc = stage_run_##name(op, P, stream)) != 1) return rc;
+    DQP_RIC_PARTS
 #undef PART
     return 1;
 }
 
-int stage_forward(const KParams &P, void *stream)
-{
-    if (ric_supported(P.mn, P.mm)) return ric_forward(P, stream);
-    if (ricw_supported(P.mn, P.mm)) return ricw_forward(P, stream);
-    return P.dynId ? 1 : ric_host_run(RIC_HOST_FORWARD, P, stream);
-}
-
-int stage_forward_stepped(const KParams &P, void *stream)
-{
-    if (ric_supported(P.mn, P.mm)) return ric_forward_stepped(P, stream);
-    if (ricw_supported(P.mn, P.mm)) return ricw_forward_stepped(P, stream);
-    return ric_host_run(RIC_HOST_STEPPED, P, stream);
-}
-
-int stage_backward(const KParams &P, void *stream)
-{
-    if (ric_supported(P.mn, P.mm)) return ric_backward(P, stream);
-    if (ricw_supported(P.mn, P.mm)) return ricw_backward(P, stream);
-    return ric_host_run(RIC_HOST_BACKWARD, P, stream);
-}
+int stage_forward(const KParams &P, void *stream) { return stage_run(STAGE_FORWARD, P, stream); }
+int stage_forward_stepped(const KParams &P, void *stream) { return stage_run(STAGE_STEPPED, P, stream); }
+int stage_backward(const KParams &P, void *stream) { return stage_run(STAGE_BACKWARD, P, stream); }
 
 // ---------------------------------------------------------------------------------------------
 // Region of the padded copies (doubles, every array rounded up to an even length; include/dqp.h gives the formula):
@@ -64,12 +56,6 @@ int stage_backward(const KParams &P, void *stream)
 //   f', df' (T-1, B, n')       x0', dx0' (B, n')
 // with nt' = n' + m; tau', g' = dl/dtau', nu', ry' batch-major like the caller's arrays, the rest time-major.
 static long long ev(long long x) { return (x + 1) & ~1LL; }
-
-long long pad_kernel_doubles(int np, int m, int T, int B, bool stepped)
-{
-    const int q = stage_q(np, m);
-    return (long long)((B + q - 1) / q * q) * (stage_layout_doubles(np, m, T) + (stepped ? ric::STEP_STATE : 0));
-}
 
 long long pad_region_doubles(int np, int m, int T, int B)
 {

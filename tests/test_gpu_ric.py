@@ -1,4 +1,4 @@
-"""Stage-wise (Riccati) PDIPM for MPC-structured QPs (csrc/dqp_ric.hip; SURVEY.md §8 f1 / row g,
+"""Stage-wise (Riccati) PDIPM for MPC-structured QPs (csrc/dqp_ric_kernels.h; SURVEY.md §8 f1 / row g,
 BASELINE config 4 shape n 12, m 4, T 30) through the C ABI (dqp_mpc_qp_forward / _backward).
 
 Checkers: (1) the assemble -> DenseQPFunction pipeline of this package on the dense GPU kernels
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from diff_qp_mpc_amd._build import RIC_SIZES as ALL_PAIRS      # every native 16-lane pair
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -345,10 +346,6 @@ def test_stagewise_more_size_pairs(n, m, T, B):
     nt = n + m
     dc = np.stack([og["dp"][:, t * nt:(t + 1) * nt] for t in range(T)])
     np.testing.assert_allclose(grads[1], dc, err_msg="dc", **GT)
-
-
-ALL_PAIRS = [(12, 4), (3, 3), (3, 1), (4, 1), (6, 1), (2, 1), (4, 2), (5, 1), (8, 1), (2, 2), (3, 2), (6, 2), (8, 2), (6, 3),
-             (4, 4), (8, 4), (10, 4), (12, 2)]        # DQP_RIC_SIZES of csrc/dqp_ric.hip
 
 
 @pytest.mark.parametrize("n,m,T,B", [(3, 1, 10, 9), (4, 2, 6, 130), (12, 4, 4, 6)] + [(n, m, 5, 6) for n, m in ALL_PAIRS])

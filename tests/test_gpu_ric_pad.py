@@ -1,4 +1,4 @@
-"""Padded stage-wise MPC QPs (dqp_mpc_dims.n_state_host, csrc/dqp_ric_pad.hip + csrc/dqp_ric_host.hip): a problem
+"""Padded stage-wise MPC QPs (dqp_mpc_dims.n_state_host, csrc/dqp_ric_pad.hip, the host parts of csrc/dqp_ric.hip): a problem
 (n, m) solved by the kernels of a compiled pair (n', m) with n' - n dummy states.
 
 Checkers: (1) on compiled pairs, the padded solve against the native one (both termination rules, partial

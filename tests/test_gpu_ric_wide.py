@@ -1,4 +1,4 @@
-"""Wide stage-wise MPC QP kernels (csrc/dqp_ric_wide.hip: 16 < n_state + n_ctrl <= 32, one QP per 32-lane
+"""Wide stage-wise MPC QP kernels (the wide part of csrc/dqp_ric.hip: 16 < n_state + n_ctrl <= 32, one QP per 32-lane
 half-wavefront) through the C ABI and qp_wrapper.MPC.
 
 Checkers, as in test_gpu_ric.py: (1) assemble -> DenseQPFunction on the dense GPU kernels where the dense QP fits

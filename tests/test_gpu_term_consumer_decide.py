@@ -7,7 +7,7 @@ I* into the header.  Expected values come from the CPU oracle, never from the ke
     random QPs converges and stops at iteration 11-13 for every seed tried (0..29), so this case runs with
     max_iter = 10: the oracle's own run is asserted to use all 10 iterations and to flag nothing;
   * the same through the families that solve again in pass 2 (dqp_r16.hip, dqp_pdipm.hip) and the stage-wise path
-    (dqp_ric.hip);
+    (dqp_ric_kernels.h);
   * a header left by an earlier call on the same termination buffer, eagerly and under graph capture and replay;
   * the multi-device entry points on one device (a positive header, written by term_decide_kernel).
 The kernels use the guarded step (batch_LU.py:203-214; tests/test_gpu_parity.py::reference_outputs), so the stop
@@ -192,7 +192,7 @@ def test_generic_kernels_solve_again_up_to_the_stop(lib, max_iter):
 
 @pytest.mark.parametrize("max_iter", [20, 6])
 def test_stagewise_kernels_finish_at_the_stop(lib, max_iter):
-    """dqp_mpc_qp_forward on the stage-wise kernels (dqp_ric.hip) at n 3, m 3, T 5, B = 9, against the oracle's
+    """dqp_mpc_qp_forward on the stage-wise kernels (dqp_ric_kernels.h) at n 3, m 3, T 5, B = 9, against the oracle's
     DenseQPFunction restatement on the assembled QP (tests/test_gpu_ric.py)."""
     from diff_qp_mpc_amd import _lib
     n, m, T, B = 3, 3, 5, 9

@@ -1,4 +1,4 @@
-"""Host side of the wide stage-wise MPC kernels (csrc/dqp_ric_wide.hip, 16 < n_state + n_ctrl <= 32): which shapes
+"""Host side of the wide stage-wise MPC kernels (csrc/dqp_mpc_qp.hip, 16 < n_state + n_ctrl <= 32): which shapes
 the library serves and the exact workspace sizes include/dqp.h documents.  Needs only the built library."""
 import ctypes
 

@@ -3,7 +3,7 @@
 replaced by a compile of each variant file (and extra -D flags), so that several versions can be timed
 in ONE gpurun call (box-to-box differences are ~10 %, larger than most single changes).
 
-    python tools/ab_variants.py build dqp_ric.hip name1=/path/to/variant1.hip[,-DX=1] name2=...
+    python tools/ab_variants.py build dqp_ric_native.o name1=/path/to/variant1.hip[,-DX=1] name2=...
     DQP_HIP_LIBRARY=diff-qp-mpc_amd/csrc/libdqp_hip_ab_name1.so python tools/bench_ric.py
 """
 import os, shutil, subprocess, sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the stage-wise MPC QP kernels (csrc/dqp_ric.hip) at the BASELINE config-4 shape:
+"""Timing of the stage-wise MPC QP kernels (csrc/dqp_ric_kernels.h) at the BASELINE config-4 shape:
 n_state 12, n_ctrl 4, T 30 (nz 480, nineq 240, neq 360), B = 8192 (BATCH), HIP events around the
 C-ABI calls dqp_mpc_qp_forward / dqp_mpc_qp_backward, both termination modes.
 HOST=n': the problem padded onto the kernels of (n', m) (dqp_mpc_dims.n_state_host), with the per-kernel split of one
