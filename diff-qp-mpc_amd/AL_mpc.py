@@ -319,36 +319,16 @@ class GraphedMPC:
 
     def __init__(self, ctrl, sample_inputs, dyn, x_init=None, u_init=None, warmup=3):
         global CHECK_CHOLESKY
-        from .qp_wrapper import _GraphReplay
+        from .qp_wrapper import _GraphReplay, _capture_graphs
         self._replay = _GraphReplay
         self.ctrl, self.dyn = ctrl, dyn
         self.x_init, self.u_init = x_init, u_init
-        self.static_inputs = tuple(t.detach().clone().requires_grad_(t.requires_grad) for t in sample_inputs)
         check, CHECK_CHOLESKY = CHECK_CHOLESKY, False
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    outs = self._call(*self.static_inputs)
-                    torch.autograd.grad(outs, self._grad_inputs(), tuple(torch.ones_like(o) for o in outs), allow_unused=True)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            pool = torch.cuda.graph_pool_handle()
-            self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.fwd_graph, pool=pool):
-                self.static_outputs = self._call(*self.static_inputs)
-                self._flags = list(ctrl.fail_log)
-            self.static_grad_outputs = tuple(torch.zeros_like(o) for o in self.static_outputs)
-            with torch.cuda.graph(self.bwd_graph, pool=pool):
-                gi = torch.autograd.grad(self.static_outputs, self._grad_inputs(), self.static_grad_outputs, allow_unused=True)
+            _capture_graphs(self, self._call, sample_inputs, warmup)
         finally:
             CHECK_CHOLESKY = check
-        it = iter(gi)
-        self.static_grad_inputs = tuple(next(it) if t.requires_grad else None for t in self.static_inputs)
-
-    def _grad_inputs(self):
-        return tuple(t for t in self.static_inputs if t.requires_grad)
+        self._flags = list(ctrl.fail_log)       # of the captured call: reinitialize() starts the log afresh
 
     def _call(self, x0, C, c):
         ctrl = self.ctrl

@@ -1,14 +1,17 @@
 """ctypes binding of the C ABI in include/dqp.h (csrc/libdqp_hip.so).
 
 The library is loaded lazily on first use and there is deliberately no fallback: a missing
-or unloadable library raises RuntimeError naming the build command.
+or unloadable library raises RuntimeError naming the build command.  The prototypes are read from
+include/dqp.h (prototypes()): the header is the one place that says what an entry point takes.  The
+structs and the few constants are written out here; tests pin the constants against the header.
 """
 import ctypes
 import os
+import re
+
+import torch
 
 from . import _build
-
-_dp = ctypes.c_void_p
 
 
 class dqp_dims(ctypes.Structure):
@@ -44,24 +47,6 @@ DQP_MAX_DIM = 64
 DQP_MAX_DIM_LARGE = 512
 SHARED_GRAD_KC = 64      # samples per split-K chunk of dqp_qp_backward_shared (csrc/dqp_shared_grad.hip: KC)
 
-# every symbol include/dqp.h declares
-SYMBOLS = ("dqp_version", "dqp_error_string", "dqp_workspace_bytes", "dqp_termination_bytes",
-           "dqp_qp_forward", "dqp_qp_backward", "dqp_qp_backward_shared_bytes", "dqp_qp_backward_shared", "dqp_term_local_masks", "dqp_qp_forward_finish", "dqp_mpc_assemble", "dqp_mpc_assemble_backward",
-           "dqp_mpc_qp_supported", "dqp_mpc_qp_workspace_bytes", "dqp_mpc_qp_host_n_state", "dqp_mpc_qp_termination_bytes", "dqp_mpc_qp_forward", "dqp_mpc_qp_backward", "dqp_mpc_line_search", "dqp_mpc_rollout_backward",
-           "dqp_al_newton_step", "dqp_al_chol_solve", "dqp_al_assemble", "dqp_al_merit",
-           "dqp_al_newton_solve_bytes", "dqp_al_newton_solve",
-           "dqp_al_outer_update", "dqp_al_banded_factor_bytes", "dqp_al_banded_newton_step", "dqp_al_banded_solve",
-           "dqp_al_banded_newton_step_jac", "dqp_al_banded_jac_factor_bytes", "dqp_al_lane_group", "dqp_al_mpc_solve_bytes", "dqp_al_mpc_solve",
-           "dqp_al_mpc_solve_fused_supported", "dqp_al_mpc_solve_fused_bytes", "dqp_al_mpc_solve_fused",
-           "dqp_mpc_qp_stepped_workspace_bytes", "dqp_mpc_qp_stepped_termination_bytes", "dqp_mpc_qp_forward_stepped", "dqp_trace_begin", "dqp_trace_end",
-           "dqp_dyn_sizes", "dqp_dyn_step", "dqp_dyn_jacobian", "dqp_dyn_forward_dynamics",
-           "dqp_dyn_forward_derivatives") + tuple(
-    # the per-sample / per-knot bound layout (dqp_al_bounds): a twin of every entry point that takes control bounds
-    s + "_bounds" for s in ("dqp_al_merit", "dqp_al_newton_solve", "dqp_al_outer_update", "dqp_al_mpc_solve",
-                            "dqp_al_mpc_solve_fused_supported", "dqp_al_mpc_solve_fused_bytes", "dqp_al_mpc_solve_fused",
-                            "dqp_al_banded_newton_step", "dqp_al_banded_newton_step_jac")) + ("dqp_al_mpc_solve_fused_lds_bytes",) + (
-    # the same for the MPC QP entry points (dqp_mpc_bounds = dqp_al_bounds, with the time-major full layout accepted too)
-    "dqp_mpc_assemble_bounds", "dqp_mpc_qp_forward_bounds", "dqp_mpc_qp_forward_stepped_bounds")
 DQP_DYN = {"pendulum1l": 1, "cartpole1l": 2, "cartpole2l": 3, "pendulum_euler": 4, "pendulum_dx": 5,
            "rexquadrotor": 6, "integrator": 7}
 
@@ -93,6 +78,44 @@ class dqp_trace_record(ctypes.Structure):
     _fields_ = [("kernel", ctypes.c_char * 248), ("ms", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_STRUCTS = {c.__name__: c for c in (dqp_dims, dqp_opts, dqp_mpc_dims, dqp_al_dims, dqp_al_mpc_dims, dqp_al_bounds,
+                                    dqp_trace_record)}
+_STRUCTS["dqp_mpc_bounds"] = dqp_al_bounds        # a typedef in the header
+
+
+def prototypes(header):
+    """{name: (restype, argtypes, parameter names)} of every `ret dqp_name(args);` in the text of include/dqp.h.
+    int, int32_t, double, size_t are the ctypes scalars, a returned `const char *` is c_char_p, a pointer to a struct
+    of this module is POINTER of it, every other pointer c_void_p; anything else is a RuntimeError naming the prototype."""
+    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([\w \t*]+?)\s*\b(dqp_\w+)\s*\(([^()]*)\)\s*;", text):
+        def ctype(decl, returned=False):
+            t = " ".join(re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split())
+            if t in _SCALARS:
+                return _SCALARS[t]
+            if returned and t == "char *":
+                return ctypes.c_char_p
+            if t.endswith(" *") and not returned:
+                base = t[:-2]
+                return ctypes.POINTER(_STRUCTS[base]) if base in _STRUCTS else ctypes.c_void_p
+            raise RuntimeError("diff_qp_mpc_amd: include/dqp.h: no ctypes rule for %r in the prototype of %s"
+                               % (" ".join(decl.split()), name))
+        argtypes, names = [], []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = re.fullmatch(r"\s*(.*?)(\w+)\s*", p, flags=re.S)
+            argtypes.append(ctype(m.group(1)))
+            names.append(m.group(2))
+        out[name] = (ctype(ret, returned=True), argtypes, tuple(names))
+    return out
+
+
+with open(os.path.join(os.path.dirname(_build.HERE), "include", "dqp.h")) as _f:
+    PROTOTYPES = prototypes(_f.read())
+SYMBOLS = tuple(PROTOTYPES)      # every symbol include/dqp.h declares
+_launches = {}                   # the entries call() serves (last parameter `stream`), filled by load()
 _lib = None
 
 
@@ -115,140 +138,47 @@ def load():
         lib = ctypes.CDLL(so)
     except OSError as e:  # pragma: no cover
         raise RuntimeError("diff_qp_mpc_amd: cannot load %s: %s" % (so, e))
-    lib.dqp_version.restype = ctypes.c_int
-    lib.dqp_error_string.restype = ctypes.c_char_p
-    lib.dqp_error_string.argtypes = [ctypes.c_int]
-    lib.dqp_workspace_bytes.restype = ctypes.c_size_t
-    lib.dqp_workspace_bytes.argtypes = [ctypes.POINTER(dqp_dims)]
-    lib.dqp_qp_forward.restype = ctypes.c_int
-    lib.dqp_termination_bytes.restype = ctypes.c_size_t
-    lib.dqp_termination_bytes.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)]
-    lib.dqp_qp_forward.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 15
-    lib.dqp_term_local_masks.restype = ctypes.c_int
-    lib.dqp_term_local_masks.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 3
-    lib.dqp_qp_forward_finish.restype = ctypes.c_int
-    lib.dqp_qp_forward_finish.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 16
-    lib.dqp_qp_backward.restype = ctypes.c_int
-    lib.dqp_qp_backward.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 17
-    lib.dqp_qp_backward_shared_bytes.restype = ctypes.c_size_t
-    lib.dqp_qp_backward_shared_bytes.argtypes = [ctypes.POINTER(dqp_dims)]
-    lib.dqp_qp_backward_shared.restype = ctypes.c_int
-    lib.dqp_qp_backward_shared.argtypes = [ctypes.POINTER(dqp_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 18
-    lib.dqp_mpc_assemble.restype = ctypes.c_int
-    lib.dqp_mpc_assemble.argtypes = [ctypes.POINTER(dqp_mpc_dims)] + [_dp] * 14
-    lib.dqp_mpc_assemble_backward.restype = ctypes.c_int
-    lib.dqp_mpc_assemble_backward.argtypes = [ctypes.POINTER(dqp_mpc_dims)] + [_dp] * 10
-    lib.dqp_mpc_qp_supported.restype = ctypes.c_int
-    lib.dqp_mpc_qp_supported.argtypes = [ctypes.POINTER(dqp_mpc_dims)]
-    lib.dqp_mpc_qp_workspace_bytes.restype = ctypes.c_size_t
-    lib.dqp_mpc_qp_workspace_bytes.argtypes = [ctypes.POINTER(dqp_mpc_dims)]
-    lib.dqp_mpc_qp_host_n_state.restype = ctypes.c_int32
-    lib.dqp_mpc_qp_host_n_state.argtypes = [ctypes.POINTER(dqp_mpc_dims)]
-    lib.dqp_mpc_qp_termination_bytes.restype = ctypes.c_size_t
-    lib.dqp_mpc_qp_termination_bytes.argtypes = [ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)]
-    lib.dqp_mpc_qp_forward.restype = ctypes.c_int
-    lib.dqp_mpc_qp_forward.argtypes = [ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 16
-    lib.dqp_mpc_qp_backward.restype = ctypes.c_int
-    lib.dqp_mpc_qp_backward.argtypes = [ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 15
-    lib.dqp_mpc_line_search.restype = ctypes.c_int
-    lib.dqp_mpc_line_search.argtypes = ([ctypes.POINTER(dqp_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 8 +
-                                        [ctypes.c_double, ctypes.c_int32] + [_dp] * 5)
-    lib.dqp_mpc_rollout_backward.restype = ctypes.c_int
-    lib.dqp_mpc_rollout_backward.argtypes = [ctypes.POINTER(dqp_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 9
-    lib.dqp_al_newton_step.restype = ctypes.c_int
-    lib.dqp_al_newton_step.argtypes = [ctypes.POINTER(dqp_al_dims)] + [_dp] * 8
-    lib.dqp_al_chol_solve.restype = ctypes.c_int
-    lib.dqp_al_chol_solve.argtypes = [ctypes.POINTER(dqp_al_dims)] + [_dp] * 4
-    lib.dqp_al_assemble.restype = ctypes.c_int
-    lib.dqp_al_assemble.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)] + [_dp] * 8
-    lib.dqp_al_merit.restype = ctypes.c_int
-    lib.dqp_al_merit.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int32] + [_dp] * 11
-    lib.dqp_al_newton_solve_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_newton_solve_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int32]
-    lib.dqp_al_newton_solve.restype = ctypes.c_int
-    lib.dqp_al_newton_solve.argtypes = ([ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double, ctypes.c_int32,
-                                         ctypes.c_int32] + [_dp] * 13)
-    lib.dqp_al_outer_update.restype = ctypes.c_int
-    lib.dqp_al_outer_update.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 12
-    lib.dqp_al_banded_factor_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_banded_factor_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int]
-    lib.dqp_al_banded_jac_factor_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_banded_jac_factor_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)]
-    lib.dqp_al_banded_newton_step.restype = ctypes.c_int
-    lib.dqp_al_banded_newton_step.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double] + [_dp] * 12
-    lib.dqp_al_banded_newton_step_jac.restype = ctypes.c_int
-    lib.dqp_al_banded_newton_step_jac.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)] + [_dp] * 15
-    lib.dqp_al_banded_solve.restype = ctypes.c_int
-    lib.dqp_al_banded_solve.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int] + [_dp] * 4
-    lib.dqp_al_mpc_solve_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_mpc_solve_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)]
-    lib.dqp_al_mpc_solve.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve.argtypes = ([ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int, ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
-                                     + [_dp] * 12 + [ctypes.c_int32] + [_dp] * 10)
-    lib.dqp_al_mpc_solve_fused_supported.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve_fused_supported.argtypes = [ctypes.POINTER(dqp_al_mpc_dims), ctypes.c_int]
-    lib.dqp_al_mpc_solve_fused_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_mpc_solve_fused_bytes.argtypes = [ctypes.POINTER(dqp_al_mpc_dims)]
-    lib.dqp_al_mpc_solve_fused.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve_fused.argtypes = lib.dqp_al_mpc_solve.argtypes
-    # the _bounds twins: the (u_lower, u_upper) pointer pair becomes one dqp_al_bounds *
-    _bp, _mp = ctypes.POINTER(dqp_al_bounds), ctypes.POINTER(dqp_al_mpc_dims)
-    lib.dqp_al_merit_bounds.restype = ctypes.c_int
-    lib.dqp_al_merit_bounds.argtypes = [_mp, ctypes.c_int32] + [_dp] * 7 + [_bp] + [_dp] * 2
-    lib.dqp_al_newton_solve_bounds.restype = ctypes.c_int
-    lib.dqp_al_newton_solve_bounds.argtypes = ([_mp, ctypes.c_int, ctypes.c_double, ctypes.c_int32, ctypes.c_int32] + [_dp] * 5
-                                               + [_bp] + [_dp] * 6)
-    lib.dqp_al_outer_update_bounds.restype = ctypes.c_int
-    lib.dqp_al_outer_update_bounds.argtypes = [_mp, ctypes.c_int, ctypes.c_double] + [_dp] * 6 + [_bp] + [_dp] * 4
-    lib.dqp_al_banded_newton_step_bounds.restype = ctypes.c_int
-    lib.dqp_al_banded_newton_step_bounds.argtypes = [_mp, ctypes.c_int, ctypes.c_double] + [_dp] * 6 + [_bp] + [_dp] * 4
-    lib.dqp_al_banded_newton_step_jac_bounds.restype = ctypes.c_int
-    lib.dqp_al_banded_newton_step_jac_bounds.argtypes = [_mp] + [_dp] * 6 + [_bp] + [_dp] * 7
-    lib.dqp_al_mpc_solve_bounds.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve_bounds.argtypes = ([_mp, ctypes.c_int, ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
-                                            + [_dp] * 5 + [_bp] + [_dp] * 5 + [ctypes.c_int32] + [_dp] * 10)
-    lib.dqp_al_mpc_solve_fused_bounds.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve_fused_bounds.argtypes = lib.dqp_al_mpc_solve_bounds.argtypes
-    lib.dqp_al_mpc_solve_fused_supported_bounds.restype = ctypes.c_int
-    lib.dqp_al_mpc_solve_fused_supported_bounds.argtypes = [_mp, ctypes.c_int, _bp]
-    lib.dqp_al_mpc_solve_fused_bytes_bounds.restype = ctypes.c_size_t
-    lib.dqp_al_mpc_solve_fused_bytes_bounds.argtypes = [_mp, _bp]
-    lib.dqp_al_mpc_solve_fused_lds_bytes.restype = ctypes.c_size_t
-    lib.dqp_al_mpc_solve_fused_lds_bytes.argtypes = [_mp, ctypes.c_int, _bp]
-    _md, _op = ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)
-    lib.dqp_mpc_assemble_bounds.restype = ctypes.c_int
-    lib.dqp_mpc_assemble_bounds.argtypes = [_md] + [_dp] * 5 + [_bp] + [_dp] * 7
-    lib.dqp_mpc_qp_forward_bounds.restype = ctypes.c_int
-    lib.dqp_mpc_qp_forward_bounds.argtypes = [_md, _op] + [_dp] * 5 + [_bp] + [_dp] * 9
-    lib.dqp_mpc_qp_forward_stepped_bounds.restype = ctypes.c_int
-    lib.dqp_mpc_qp_forward_stepped_bounds.argtypes = ([_md, _op] + [_dp] * 5 + [_bp] + [_dp] + [ctypes.c_int32, ctypes.c_int32]
-                                                      + [_dp] * 9)
-    lib.dqp_al_lane_group.restype = ctypes.c_int
-    lib.dqp_al_lane_group.argtypes = [ctypes.c_int]
-    lib.dqp_mpc_qp_stepped_workspace_bytes.restype = ctypes.c_size_t
-    lib.dqp_mpc_qp_stepped_workspace_bytes.argtypes = [ctypes.POINTER(dqp_mpc_dims)]
-    lib.dqp_mpc_qp_stepped_termination_bytes.restype = ctypes.c_size_t
-    lib.dqp_mpc_qp_stepped_termination_bytes.argtypes = [ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)]
-    lib.dqp_mpc_qp_forward_stepped.restype = ctypes.c_int
-    lib.dqp_mpc_qp_forward_stepped.argtypes = ([ctypes.POINTER(dqp_mpc_dims), ctypes.POINTER(dqp_opts)] + [_dp] * 8 +
-                                               [ctypes.c_int32, ctypes.c_int32] + [_dp] * 9)
-    lib.dqp_trace_begin.restype = ctypes.c_int
-    lib.dqp_trace_begin.argtypes = [ctypes.c_int32]
-    lib.dqp_trace_end.restype = ctypes.c_int
-    lib.dqp_trace_end.argtypes = [ctypes.POINTER(dqp_trace_record), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    lib.dqp_dyn_sizes.restype = ctypes.c_int
-    lib.dqp_dyn_sizes.argtypes = [ctypes.c_int, i32p, i32p]
-    lib.dqp_dyn_step.restype = ctypes.c_int
-    lib.dqp_dyn_step.argtypes = [ctypes.c_int, ctypes.c_int32, _dp, _dp, ctypes.c_double, _dp, _dp]
-    lib.dqp_dyn_jacobian.restype = ctypes.c_int
-    lib.dqp_dyn_jacobian.argtypes = [ctypes.c_int, ctypes.c_int32, _dp, _dp, ctypes.c_double] + [_dp] * 4
-    lib.dqp_dyn_forward_dynamics.restype = ctypes.c_int
-    lib.dqp_dyn_forward_dynamics.argtypes = [ctypes.c_int, ctypes.c_int32] + [_dp] * 7
-    lib.dqp_dyn_forward_derivatives.restype = ctypes.c_int
-    lib.dqp_dyn_forward_derivatives.argtypes = [ctypes.c_int, ctypes.c_int32] + [_dp] * 11
+    for name, (restype, argtypes, params) in PROTOTYPES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError("diff_qp_mpc_amd: %s does not export %s, which include/dqp.h declares" % (so, name))
+        fn.restype, fn.argtypes = restype, argtypes
+        if params and params[-1] == "stream":
+            _launches[name] = fn
     _lib = lib
     return lib
+
+
+def call(name, dev, *args):
+    """The one way the package launches: lib.<name>(*args, current stream of `dev`) under torch.cuda.device(dev), for
+    the entries whose last parameter is `stream`; a return code other than DQP_OK raises, naming the entry.  A
+    torch.Tensor goes in as its data pointer (None or an empty tensor as NULL; a tensor that is not on a GPU is
+    refused), a ctypes.Structure by reference, anything else (ints, floats, DeviceBounds.ref()) as it is.  Callers hand
+    over the tensors themselves, so `args` references every converted temporary until the call has been enqueued."""
+    fn = _launches.get(name)
+    if fn is None:                  # the first call, or not a launching entry
+        load()
+        if name not in _launches:
+            raise RuntimeError("diff_qp_mpc_amd: %s is not an entry point of include/dqp.h that takes a stream" % name)
+        fn = _launches[name]
+    conv = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                a = a.data_ptr()            # 0 for an empty tensor
+            elif a.numel() == 0:
+                a = None
+            else:
+                raise RuntimeError("diff_qp_mpc_amd runs only on a GPU (HIP): %s got a %s tensor. "
+                                   "There is no CPU fallback." % (name, a.device))
+        elif isinstance(a, ctypes.Structure):
+            a = ctypes.byref(a)
+        conv.append(a)
+    with torch.cuda.device(dev):
+        rc = fn(*conv, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != DQP_OK:
+        check(rc, name)
 
 
 def check(rc, what):

@@ -38,19 +38,6 @@ N_LINESEARCH = 20          # al_utils.py:504
 MAX_NEWTON_STEPS = 4       # al_utils.py:391
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _need_gpu(t):
-    if not t.is_cuda:
-        raise RuntimeError("diff_qp_mpc_amd AL solver runs only on a GPU (HIP); there is no CPU fallback.")
-
-
 # ------------------------------------------------------------------------------------------
 # control bounds per sample and per knot: the layout the kernels index (include/dqp.h: dqp_al_bounds)
 # ------------------------------------------------------------------------------------------
@@ -305,9 +292,7 @@ def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_up
 def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper):
     """merit_function through dqp_al_merit: the dynamics are evaluated by the caller's module (one
     batched call over all candidates), cost + penalty + multiplier terms in one launch."""
-    lib = _lib.load()
-    cand = xu.dim() == 4
-    k = xu.shape[0] if cand else 1
+    k = xu.shape[0] if xu.dim() == 4 else 1
     flat = xu.reshape(-1, *xu.shape[-2:])
     n = x0.shape[-1]
     B, T, nt = x0.shape[0], flat.shape[1], flat.shape[2]
@@ -320,15 +305,9 @@ def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper):
     xu64, xn64 = d64(flat), d64(x_next)
     merit = torch.empty(k * B, dtype=torch.float64, device=xu.device)
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
-    # the converted inputs must outlive the launch: a temporary freed right after data_ptr() is
-    # handed back to the caching allocator and overwritten by the NEXT conversion before the
-    # kernel (enqueued after all of them) reads it
     keep = [d64(x0), d64(Q), d64(q), d64(lamda), d64(rho).reshape(B)]
     bd = bounds_layout(u_lower, u_upper, B, T, m)
-    with torch.cuda.device(xu.device):
-        rc = lib.dqp_al_merit_bounds(ctypes.byref(dims), k, _ptr(xu64), _ptr(xn64), *[_ptr(t) for t in keep], bd.ref(),
-                                     _ptr(merit), _stream(xu.device))
-    _lib.check(rc, "dqp_al_merit_bounds")
+    _lib.call("dqp_al_merit_bounds", xu.device, dims, k, xu64, xn64, *keep, bd.ref(), merit)
     return merit.to(xu.dtype)
 
 
@@ -355,7 +334,6 @@ def assemble_jacobian(xu, x0, dx_jac, lamda, rho, u_lower, u_upper):
     """Clamped constraint Jacobian Jc (B,ncon,nz) and J^T lam + rho Jc^T res_c (B,nz) in one
     launch (dqp_al_assemble) from the per-knot dynamics Jacobians -- the fused form of
     constraint_jacobian() + the two bmm's the reference does (al_utils.py:62-102,162-318)."""
-    lib = _lib.load()
     n = x0.shape[-1]
     B, T, nt = xu.shape
     m = nt - n
@@ -364,7 +342,6 @@ def assemble_jacobian(xu, x0, dx_jac, lamda, rho, u_lower, u_upper):
     eq = torch.cat((x[:, 1:] - x_next.view(B, T - 1, n), x[:, :1] - x0[:, None]), 1).reshape(B, -1)
     _, iqc = dyn_res_ineq(x, u, x0, None, None, u_lower, u_upper)
     resc = torch.cat((eq, iqc), 1).detach().double().contiguous()
-    _need_gpu(resc)
     Jx = Jx.detach().double().reshape(B, T - 1, n, n).contiguous()
     Ju = Ju.detach().double().reshape(B, T - 1, n, m).contiguous()
     lam = lamda.detach().double().contiguous()
@@ -374,10 +351,7 @@ def assemble_jacobian(xu, x0, dx_jac, lamda, rho, u_lower, u_upper):
     Jc = torch.empty(B, ncon, nz, dtype=torch.float64, device=dev)
     gterm = torch.empty(B, nz, dtype=torch.float64, device=dev)
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
-    with torch.cuda.device(dev):
-        rc = lib.dqp_al_assemble(ctypes.byref(dims), _ptr(Jx), _ptr(Ju), _ptr(lam), _ptr(resc), _ptr(rh),
-                                 _ptr(Jc), _ptr(gterm), _stream(dev))
-    _lib.check(rc, "dqp_al_assemble")
+    _lib.call("dqp_al_assemble", dev, dims, Jx, Ju, lam, resc, rh, Jc, gterm)
     return Jc, gterm
 
 
@@ -386,9 +360,7 @@ def assemble_jacobian(xu, x0, dx_jac, lamda, rho, u_lower, u_upper):
 # ------------------------------------------------------------------------------------------
 def newton_step(terms, grad):
     """-> (update = -H^-1 grad, L, info) through dqp_al_newton_step."""
-    lib = _lib.load()
     Jc = terms.Jc.detach().double().contiguous()
-    _need_gpu(Jc)
     B, ncon, nz = Jc.shape
     Qd = terms.Qd.detach().double().contiguous()
     rho = terms.rho.detach().double().reshape(B).contiguous()
@@ -398,25 +370,18 @@ def newton_step(terms, grad):
     L = torch.empty(B, nz, nz, dtype=torch.float64, device=dev)
     info = torch.empty(B, dtype=torch.int32, device=dev)
     dims = _lib.dqp_al_dims(B, nz, ncon, 0)
-    with torch.cuda.device(dev):
-        rc = lib.dqp_al_newton_step(ctypes.byref(dims), _ptr(Jc), _ptr(Qd), _ptr(rho), _ptr(g),
-                                    _ptr(upd), _ptr(L), _ptr(info), _stream(dev))
-    _lib.check(rc, "dqp_al_newton_step")
+    _lib.call("dqp_al_newton_step", dev, dims, Jc, Qd, rho, g, upd, L, info)
     return upd, L, info
 
 
 def chol_solve_neg(L, rhs):
     """-(L L^T)^-1 rhs through dqp_al_chol_solve."""
-    lib = _lib.load()
     L = L.contiguous()
-    _need_gpu(L)
     B, nz, _ = L.shape
     r = rhs.detach().double().reshape(B, nz).contiguous()
     out = torch.empty_like(r)
     dims = _lib.dqp_al_dims(B, nz, 0, 0)
-    with torch.cuda.device(L.device):
-        rc = lib.dqp_al_chol_solve(ctypes.byref(dims), _ptr(L), _ptr(r), _ptr(out), _stream(L.device))
-    _lib.check(rc, "dqp_al_chol_solve")
+    _lib.call("dqp_al_chol_solve", L.device, dims, L, r, out)
     return out
 
 
@@ -497,6 +462,15 @@ class NewtonAL(torch.autograd.Function):
         return (None,) * 8 + (g * x, g, None, None, None)
 
 
+def _banded_solve(dims, dyn_id, factor, x_grad):
+    """NewtonAL.backward through the block-tridiagonal factor of the last Newton step (dqp_al_banded_solve; dyn_id 0:
+    the factor of dqp_al_banded_newton_step_jac): -> -(L L^T)^-1 x_grad, fp64 (al_utils.py:477-480)."""
+    rhs = x_grad.detach().double().contiguous()
+    g = torch.empty_like(rhs)
+    _lib.call("dqp_al_banded_solve", rhs.device, dims, dyn_id, factor, rhs, g)
+    return g
+
+
 def banded_jac_supported(B, n, m, T, strided=False):
     """A block-tridiagonal Newton step exists for caller-linearised dynamics of these sizes (n + m <= 16: 8- / 16-lane
     kernels; the wide pairs up to n + m = 32: one problem per half-wavefront).  `strided`: with per-sample / per-knot
@@ -541,13 +515,8 @@ class NewtonALBandedJac(torch.autograd.Function):
                 xs = xu[:, :-1, :n].reshape(-1, n).to(xi.dtype).requires_grad_(True)
                 us = xu[:, :-1, n:].reshape(-1, m).to(xi.dtype).requires_grad_(True)
                 x_next, (Jx, Ju) = dx_jac(xs, us)
-            hold = [d64(x_next), d64(Jx), d64(Ju)]
-            with torch.cuda.device(dev):
-                rc = lib.dqp_al_banded_newton_step_jac_bounds(ctypes.byref(dims), _ptr(xu), _ptr(keep[0]), _ptr(keep[1]),
-                                                              _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4]), bd.ref(),
-                                                              _ptr(hold[0]), _ptr(hold[1]), _ptr(hold[2]), _ptr(upd), _ptr(fac),
-                                                              _ptr(info), _stream(dev))
-            _lib.check(rc, "dqp_al_banded_newton_step_jac_bounds")
+            _lib.call("dqp_al_banded_newton_step_jac_bounds", dev, dims, xu, *keep, bd.ref(), d64(x_next), d64(Jx), d64(Ju),
+                      upd, fac, info)
             if bool((info != 0).any()):     # a pivot was not positive: the reference switches to an LU solve
                 failed = True               # (al_utils.py:419-427); here the caller re-runs the dense path
                 break
@@ -567,12 +536,7 @@ class NewtonALBandedJac(torch.autograd.Function):
     @staticmethod
     def backward(ctx, x_grad, status_grad, failed_grad):
         fac, x = ctx.saved_tensors
-        rhs = x_grad.detach().double().contiguous()
-        g = torch.empty_like(rhs)
-        with torch.cuda.device(rhs.device):
-            rc = _lib.load().dqp_al_banded_solve(ctypes.byref(ctx.dims), 0, _ptr(fac), _ptr(rhs), _ptr(g), _stream(rhs.device))
-        _lib.check(rc, "dqp_al_banded_solve")
-        g = g.to(x_grad.dtype)
+        g = _banded_solve(ctx.dims, 0, fac, x_grad).to(x_grad.dtype)
         # diagonal cost: dQ = g * x, dq = g                          al_utils.py:482-485
         return (None,) * 6 + (g * x, g, None, None, None)
 
@@ -604,11 +568,8 @@ class NewtonALDevice(torch.autograd.Function):
         status = torch.empty(B, **kw)
         fail = torch.zeros(1, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_newton_solve_bytes(ctypes.byref(dims), banded)) // 8 + 1, **kw)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_al_newton_solve_bounds(ctypes.byref(dims), dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded,
-                                                *[_ptr(t) for t in keep], bd.ref(), _ptr(xu), _ptr(L), _ptr(status),
-                                                _ptr(fail), _ptr(ws), _stream(dev))
-        _lib.check(rc, "dqp_al_newton_solve_bounds")
+        _lib.call("dqp_al_newton_solve_bounds", dev, dims, dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded, *keep, bd.ref(),
+                  xu, L, status, fail, ws)
         ctx.slow_ctx = None
         if fail_sink is not None:           # the caller checks all flags once, at the end of its solve
             fail_sink.append(fail)
@@ -630,13 +591,7 @@ class NewtonALDevice(torch.autograd.Function):
             return (None,) * 4 + (gQ, gq) + (None,) * 5
         L, x = ctx.saved_tensors
         if ctx.banded:
-            rhs = x_grad.detach().double().contiguous()
-            g = torch.empty_like(rhs)
-            with torch.cuda.device(rhs.device):
-                rc = _lib.load().dqp_al_banded_solve(ctypes.byref(ctx.dims), ctx.dyn_id, _ptr(L), _ptr(rhs), _ptr(g),
-                                                     _stream(rhs.device))
-            _lib.check(rc, "dqp_al_banded_solve")
-            g = g.to(x_grad.dtype)
+            g = _banded_solve(ctx.dims, ctx.dyn_id, L, x_grad).to(x_grad.dtype)
         else:
             g = chol_solve_neg(L, x_grad).reshape(x_grad.shape).to(x_grad.dtype)
         return (None,) * 4 + (g * x.to(x_grad.dtype), g) + (None,) * 5      # al_utils.py:482-485
@@ -662,7 +617,6 @@ class ALSolveDevice(torch.autograd.Function):
         keep = [d64(x_init), d64(u_init), d64(x0), d64(Q), d64(q)]
         keep2 = [d64(lam), d64(rho).reshape(B)]
         bd = bounds_layout(u_lower, u_upper, B, T, m)
-        _need_gpu(keep[0])
         pc, pl, pr = (d64(t) for t in prev) if prev is not None else (None, None, None)
         n_prev = pc.shape[0] if prev is not None else 0
         dims = _lib.dqp_al_mpc_dims(B, n, m, T)
@@ -673,13 +627,9 @@ class ALSolveDevice(torch.autograd.Function):
         L = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), dyn.id)) // 8, **kw)
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8 + 1, **kw)
-        entry, name = ((lib.dqp_al_mpc_solve_fused_bounds, "dqp_al_mpc_solve_fused_bounds") if fused
-                       else (lib.dqp_al_mpc_solve_bounds, "dqp_al_mpc_solve_bounds"))
-        with torch.cuda.device(dev):
-            rc = entry(ctypes.byref(dims), dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *[_ptr(t) for t in keep], bd.ref(),
-                       *[_ptr(t) for t in keep2], _ptr(pc), _ptr(pl), _ptr(pr), n_prev, _ptr(xu), _ptr(hc), _ptr(hl), _ptr(hr), _ptr(resn),
-                       _ptr(L), _ptr(status), _ptr(fail), _ptr(ws), _stream(dev))
-        _lib.check(rc, name)
+        _lib.call("dqp_al_mpc_solve_fused_bounds" if fused else "dqp_al_mpc_solve_bounds", dev, dims, dyn.id, dyn.dt,
+                  al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn, L, status,
+                  fail, ws)
         ctx.dims, ctx.dyn_id = dims, dyn.id
         ctx.save_for_backward(L, xu)
         ctx.mark_non_differentiable(hc, hl, hr, resn, fail)
@@ -688,11 +638,7 @@ class ALSolveDevice(torch.autograd.Function):
     @staticmethod
     def backward(ctx, x_grad, *unused):
         L, x = ctx.saved_tensors
-        rhs = x_grad.detach().double().contiguous()
-        g = torch.empty_like(rhs)
-        with torch.cuda.device(rhs.device):
-            rc = _lib.load().dqp_al_banded_solve(ctypes.byref(ctx.dims), ctx.dyn_id, _ptr(L), _ptr(rhs), _ptr(g), _stream(rhs.device))
-        _lib.check(rc, "dqp_al_banded_solve")
+        g = _banded_solve(ctx.dims, ctx.dyn_id, L, x_grad)
         return (None,) * 3 + (g * x, g) + (None,) * 8                      # al_utils.py:482-485
 
 
@@ -718,10 +664,7 @@ def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper):
     kw = dict(dtype=torch.float64, device=dev)
     lam_new, cost, resn = torch.empty_like(keep[2]), torch.empty(B, **kw), torch.empty(B, **kw)
     dims = _lib.dqp_al_mpc_dims(B, dyn.n_state, dyn.n_ctrl, T)
-    with torch.cuda.device(dev):
-        rc = lib.dqp_al_outer_update_bounds(ctypes.byref(dims), dyn.id, dyn.dt, *[_ptr(t) for t in keep], bd.ref(),
-                                            _ptr(lam_new), _ptr(cost), _ptr(resn), _stream(dev))
-    _lib.check(rc, "dqp_al_outer_update_bounds")
+    _lib.call("dqp_al_outer_update_bounds", dev, dims, dyn.id, dyn.dt, *keep, bd.ref(), lam_new, cost, resn)
     return lam_new.to(lam.dtype), cost.to(xu.dtype), resn.to(xu.dtype)
 
 

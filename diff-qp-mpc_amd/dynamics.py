@@ -27,18 +27,7 @@ DEFAULT_DT = {"pendulum1l": 0.05, "cartpole1l": 0.05, "cartpole2l": 0.05, "pendu
 assert set(ALL_NAMES) == set(_lib.DQP_DYN) == set(DEFAULT_DT)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _gpu64(t, cols):
-    if not t.is_cuda:
-        raise RuntimeError("diff_qp_mpc_amd device dynamics run only on a GPU (HIP); got a %s tensor. "
-                           "There is no CPU fallback." % t.device)
     t = t.detach()
     if t.dtype != torch.float64:
         t = t.double()
@@ -84,10 +73,7 @@ class DeviceDynamics(torch.nn.Module):
     # ---- raw kernels on contiguous fp64 device tensors
     def _step(self, x64, u64):
         out = torch.empty_like(x64)
-        with torch.cuda.device(x64.device):
-            rc = _lib.load().dqp_dyn_step(self.id, x64.shape[0], _ptr(x64), _ptr(u64), self.dt, _ptr(out),
-                                          _stream(x64.device))
-        _lib.check(rc, "dqp_dyn_step")
+        _lib.call("dqp_dyn_step", x64.device, self.id, x64.shape[0], x64, u64, self.dt, out)
         return out
 
     def _jac(self, x64, u64, want_next=True):
@@ -95,10 +81,7 @@ class DeviceDynamics(torch.nn.Module):
         xn = torch.empty_like(x64) if want_next else None
         Jx = torch.empty(N, n, n, dtype=torch.float64, device=x64.device)
         Ju = torch.empty(N, n, m, dtype=torch.float64, device=x64.device)
-        with torch.cuda.device(x64.device):
-            rc = _lib.load().dqp_dyn_jacobian(self.id, N, _ptr(x64), _ptr(u64), self.dt, _ptr(xn), _ptr(Jx),
-                                              _ptr(Ju), _stream(x64.device))
-        _lib.check(rc, "dqp_dyn_jacobian")
+        _lib.call("dqp_dyn_jacobian", x64.device, self.id, N, x64, u64, self.dt, xn, Jx, Ju)
         return xn, Jx, Ju
 
     # ---- the callables the MPC layers take
@@ -123,10 +106,7 @@ class DeviceDynamics(torch.nn.Module):
         q64, v64, t64 = _gpu64(q, nq), _gpu64(qdot, nq), _gpu64(tau, nq)
         h64 = _gpu64(h, 1).reshape(-1)
         qo, vo = torch.empty_like(q64), torch.empty_like(q64)
-        with torch.cuda.device(q64.device):
-            rc = _lib.load().dqp_dyn_forward_dynamics(self.id, q64.shape[0], _ptr(q64), _ptr(v64), _ptr(t64),
-                                                      _ptr(h64), _ptr(qo), _ptr(vo), _stream(q64.device))
-        _lib.check(rc, "dqp_dyn_forward_dynamics")
+        _lib.call("dqp_dyn_forward_dynamics", q64.device, self.id, q64.shape[0], q64, v64, t64, h64, qo, vo)
         return qo, vo
 
     def forward_derivatives(self, q, qdot, tau, h):
@@ -135,10 +115,7 @@ class DeviceDynamics(torch.nn.Module):
         h64 = _gpu64(h, 1).reshape(-1)
         N = q64.shape[0]
         blocks = [torch.empty(N, nq, nq, dtype=torch.float64, device=q64.device) for _ in range(6)]
-        with torch.cuda.device(q64.device):
-            rc = _lib.load().dqp_dyn_forward_derivatives(self.id, N, _ptr(q64), _ptr(v64), _ptr(t64), _ptr(h64),
-                                                         *[_ptr(b) for b in blocks], _stream(q64.device))
-        _lib.check(rc, "dqp_dyn_forward_derivatives")
+        _lib.call("dqp_dyn_forward_derivatives", q64.device, self.id, N, q64, v64, t64, h64, *blocks)
         return blocks
 
 

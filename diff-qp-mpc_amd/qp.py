@@ -97,14 +97,6 @@ class QPSolvers(Enum):
     CVXPY = 2
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(0)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _prep(t, nd):
     """-> (contiguous fp64 tensor, batch stride in elements; 0 when shared)."""
     t = t.detach()
@@ -120,16 +112,7 @@ def _prep(t, nd):
     raise RuntimeError("Unexpected number of dimensions.")
 
 
-def _require_gpu(*ts):
-    for t in ts:
-        if t is not None and t.numel() > 0 and not t.is_cuda:
-            raise RuntimeError(
-                "diff_qp_mpc_amd operators run only on a GPU (HIP); got a %s tensor. "
-                "There is no CPU fallback." % t.device)
-
-
 def _forward_impl(Q_, p_, G_, h_, A_, b_, eps, maxIter, notImprovedLim, termination=None, dyn=None):
-    _require_gpu(Q_, p_, G_, h_, A_, b_)
     termination = termination or TERMINATION
     if termination not in ("batch", "per_problem"):
         raise ValueError("termination must be 'batch' or 'per_problem'")
@@ -168,8 +151,7 @@ def _forward_impl(Q_, p_, G_, h_, A_, b_, eps, maxIter, notImprovedLim, terminat
     ws = torch.empty(wsb // 8, **kw) if wsb > 0 else None
     tb = int(lib.dqp_termination_bytes(ctypes.byref(dims), ctypes.byref(opts)))
     term = torch.empty((tb + 7) // 8, **kw) if tb > 0 else None
-    args = (_ptr(Q), _ptr(p), _ptr(G), _ptr(h), _ptr(A), _ptr(b), _ptr(zhat), _ptr(lam), _ptr(nu), _ptr(slack),
-            _ptr(info), _ptr(resid), _ptr(ws), _ptr(term))
+    args = (Q, p, G, h, A, b, zhat, lam, nu, slack, info, resid, ws, term)
     if termination == "batch" and MASK_EXCHANGE is not None:
         # this batch is a shard of a larger one (sharding.global_batch_rule): pass 1, this shard's three
         # iteration masks, the caller's OR over the shards (24 bytes), the rule on the combined masks, pass 2
@@ -177,19 +159,12 @@ def _forward_impl(Q_, p_, G_, h_, A_, b_, eps, maxIter, notImprovedLim, terminat
         if dyn is not None:
             opts1.dyn_id, opts1.dyn_T, opts1.dyn_dt, opts1.dyn_x0 = opts.dyn_id, opts.dyn_T, opts.dyn_dt, opts.dyn_x0
         masks = torch.zeros(3, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_qp_forward(ctypes.byref(dims), ctypes.byref(opts1), *args, _stream(dev))
-            _lib.check(rc, "dqp_qp_forward (pass 1)")
-            _lib.check(lib.dqp_term_local_masks(ctypes.byref(dims), ctypes.byref(opts), _ptr(term), _ptr(masks),
-                                                _stream(dev)), "dqp_term_local_masks")
+        _lib.call("dqp_qp_forward", dev, dims, opts1, *args)                     # pass 1
+        _lib.call("dqp_term_local_masks", dev, dims, opts, term, masks)
         masks = MASK_EXCHANGE(masks).contiguous()
-        with torch.cuda.device(dev):
-            rc = lib.dqp_qp_forward_finish(ctypes.byref(dims), ctypes.byref(opts), *args, _ptr(masks), _stream(dev))
-        _lib.check(rc, "dqp_qp_forward_finish")
+        _lib.call("dqp_qp_forward_finish", dev, dims, opts, *args, masks)
     else:
-        with torch.cuda.device(dev):
-            rc = lib.dqp_qp_forward(ctypes.byref(dims), ctypes.byref(opts), *args, _stream(dev))
-        _lib.check(rc, "dqp_qp_forward")
+        _lib.call("dqp_qp_forward", dev, dims, opts, *args)
     # the workspace now holds the factorisation context backward can restart from (include/dqp.h)
     # (only the null-space kernels leave one: not the forced families, not the true-dynamics path)
     big = max(nz, nineq, neq) > _lib.DQP_MAX_DIM         # one QP per workgroup, matrices in the workspace (dqp_big.hip)
@@ -219,23 +194,16 @@ def _backward_impl(saved, zhat, lam, nu, slack, dl_dzhat, need, flags, shared=No
     if ctx_ws is not None and (big or not (FORCE_FLAGS & (_lib.DQP_FLAG_NO_NULLSPACE | _lib.DQP_FLAG_GENERIC_ONLY))):
         flags |= _lib.DQP_FLAG_BACKWARD_CTX
     opts = _lib.dqp_opts(0.0, 0.0, 0, 0, flags | FORCE_FLAGS, 0)
-    args = (ctypes.byref(dims), ctypes.byref(opts), _ptr(Q), _ptr(G), _ptr(A),
-            _ptr(zhat), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(g),
-            _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
-            ctypes.c_void_p(0), _ptr(ctx_ws))
+    args = (dims, opts, Q, G, A, zhat, lam, nu, slack, g, dQ, dp, dG, dh, dA, db, None, ctx_ws)
     if any(shared):
         # `dims` carries stride 0 for exactly the parameters without a batch dimension (_prep)
         strides = (dims.stride_Q, dims.stride_p, dims.stride_G, dims.stride_h, dims.stride_A, dims.stride_b)
         assert all(st == 0 for st, sh in zip(strides, shared) if sh)
         rb = int(lib.dqp_qp_backward_shared_bytes(ctypes.byref(dims)))
         reduce_ws = torch.empty(rb // 8, **kw)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_qp_backward_shared(*args, _ptr(reduce_ws), _stream(dev))
-        _lib.check(rc, "dqp_qp_backward_shared")
+        _lib.call("dqp_qp_backward_shared", dev, *args, reduce_ws)
     else:
-        with torch.cuda.device(dev):
-            rc = lib.dqp_qp_backward(*args, _stream(dev))
-        _lib.check(rc, "dqp_qp_backward")
+        _lib.call("dqp_qp_backward", dev, *args)
     return dQ, dp, dG, dh, dA, db
 
 

@@ -32,6 +32,7 @@ from torch.nn import Module
 from . import _lib
 from .al_utils import mpc_bounds_layout
 from .dynamics import DeviceDynamics, DynamicsResidual
+from . import qp as qpmod
 from .qp import DenseQPFunction
 
 
@@ -39,6 +40,16 @@ class QuadCost(NamedTuple):
     """Quadratic stage cost 1/2 tau^T C tau + c^T tau (same fields as the reference's type)."""
     C: Optional[torch.Tensor] = None
     c: Optional[torch.Tensor] = None
+
+
+class Route(NamedTuple):
+    """How MPC.single_qp solves its QP (MPC._route): `kind` is "stepped" (_MPCQPStepped: a caller's dynamics module),
+    "fused" (_MPCQP on the shape's own kernels), "padded" (_MPCQP on the stage-wise kernels of a larger host pair) or
+    "dense" (_AssembleDenseQP + DenseQPFunction)."""
+    kind: str
+    n_state_host: int = 0                       # stepped / padded: the host pair's n_state; 0: the native kernels
+    model: Optional[DeviceDynamics] = None      # the registered model whose true residual the solver evaluates
+    goal_rows: bool = False                     # dense: n_state equality rows pin the last state to zero
 
 
 class LinDx(NamedTuple):
@@ -69,14 +80,6 @@ def bmv(X, y):
     return torch.matmul(X, y[..., None])[..., 0]
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 # OR-ed into dqp_opts.flags of dqp_mpc_qp_forward (tests: DQP_FLAG_RIC_GLOBAL_WS pins the stage-wise kernels'
 # workspace to the caller's buffer where the default keeps it in LDS)
 EXTRA_FLAGS = 0
@@ -87,11 +90,6 @@ class _AssembleDenseQP(Function):
 
     @staticmethod
     def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T):
-        lib = _lib.load()
-        for t in (C, c, F, f, x0):
-            if not t.is_cuda:
-                raise RuntimeError("diff_qp_mpc_amd.qp_wrapper.MPC runs only on a GPU (HIP); "
-                                   "there is no CPU fallback.")
         dev = x0.device
         B = x0.shape[0]
         nt = n_state + n_ctrl
@@ -101,17 +99,14 @@ class _AssembleDenseQP(Function):
         cv = lambda t: t.detach().double().contiguous()
         Cc, cc, Fc, fc, xc = cv(C), cv(c), cv(F), cv(f), cv(x0)
         # per-sample / per-knot bounds in their own layout (al_utils.mpc_bounds_layout names the accepted shapes)
-        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl) if bounds else _lib.dqp_al_bounds(None, None, 0, 0)
+        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl) if bounds else None
         kw = dict(dtype=torch.float64, device=dev)
         Q = torch.empty(B, nz, nz, **kw); p = torch.empty(B, nz, **kw)
         G = torch.empty(B, nineq, nz, **kw); h = torch.empty(B, nineq, **kw)
         A = torch.empty(B, neq, nz, **kw); b = torch.empty(B, neq, **kw)
         dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1 if bounds else 0, 0)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_assemble_bounds(ctypes.byref(dims), _ptr(Cc), _ptr(cc), _ptr(Fc), _ptr(fc),
-                                             _ptr(xc), bl.ref() if bounds else ctypes.byref(bl), _ptr(Q), _ptr(p), _ptr(G),
-                                             _ptr(h), _ptr(A), _ptr(b), _stream(dev))
-        _lib.check(rc, "dqp_mpc_assemble_bounds")
+        _lib.call("dqp_mpc_assemble_bounds", dev, dims, Cc, cc, Fc, fc, xc,
+                  bl.ref() if bounds else _lib.dqp_al_bounds(None, None, 0, 0), Q, p, G, h, A, b)
         ctx.dims = dims
         ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
         ctx.dtype = x0.dtype
@@ -120,20 +115,70 @@ class _AssembleDenseQP(Function):
 
     @staticmethod
     def backward(ctx, dQ, dp, dG, dh, dA, db):
-        lib = _lib.load()
         dims = ctx.dims
         dev = next(t for t in (dQ, dp, dA, db) if t is not None).device
         kw = dict(dtype=torch.float64, device=dev)
         need = ctx.needs_input_grad
         outs = [torch.empty(s, **kw) if need[i] else None for i, s in enumerate(ctx.shapes)]
         cv = lambda t: None if t is None else t.double().contiguous()
-        dQ, dp, dA, db = cv(dQ), cv(dp), cv(dA), cv(db)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_assemble_backward(ctypes.byref(dims), _ptr(dQ), _ptr(dp), _ptr(dA),
-                                               _ptr(db), *[_ptr(o) for o in outs], _stream(dev))
-        _lib.check(rc, "dqp_mpc_assemble_backward")
+        _lib.call("dqp_mpc_assemble_backward", dev, dims, cv(dQ), cv(dp), cv(dA), cv(db), *outs)
         outs = [None if o is None else o.to(ctx.dtype) for o in outs]
         return (*outs, None, None, None, None, None)
+
+
+def _mpc_qp_forward(ctx, C, c, F, f, x0, u_lower, u_upper, dims, dyn_dt=0.0, residual=None):
+    """The forward of _MPCQP (one dqp_mpc_qp_forward_bounds call) and, with `residual`, of _MPCQPStepped (one
+    dqp_mpc_qp_forward_stepped_bounds call per PDIPM iteration, the caller's residual evaluated on the iterate in
+    between): inputs as fp64, dqp_opts, outputs, workspace and termination buffer, and what the backward needs."""
+    lib = _lib.load()
+    dev, B, T, n, m = x0.device, dims.nbatch, dims.T, dims.n_state, dims.n_ctrl
+    cv = lambda t: t.detach().double().contiguous()
+    keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
+    bl = mpc_bounds_layout(u_lower, u_upper, B, T, m)      # per sample / per knot: names the accepted shapes
+    max_iter = 20
+    batch = qpmod.TERMINATION == "batch"
+    opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, max_iter, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
+    opts.dyn_dt = dyn_dt
+    kw = dict(dtype=torch.float64, device=dev)
+    tau = torch.empty(B, T, n + m, **kw)
+    lam = torch.empty(B, 2 * T * m, **kw); slack = torch.empty(B, 2 * T * m, **kw)
+    nu = torch.empty(B, T * n, **kw)
+    info = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    resid = torch.empty(B, **kw)
+    ws_bytes, term_bytes = ((lib.dqp_mpc_qp_workspace_bytes, lib.dqp_mpc_qp_termination_bytes) if residual is None else
+                            (lib.dqp_mpc_qp_stepped_workspace_bytes, lib.dqp_mpc_qp_stepped_termination_bytes))
+    ws = torch.empty(int(ws_bytes(ctypes.byref(dims))) // 8, **kw)
+    tb = int(term_bytes(ctypes.byref(dims), ctypes.byref(opts)))
+    term = torch.empty((tb + 7) // 8, **kw) if tb else None
+    head, tail = (dims, opts, *keep, bl.ref()), (tau, lam, nu, slack, info, resid, ws, term)
+    if residual is None:
+        _lib.call("dqp_mpc_qp_forward_bounds", dev, *head, *tail)
+    else:
+        with torch.no_grad():
+            _lib.call("dqp_mpc_qp_forward_stepped_bounds", dev, *head, None, 0, 0, *tail)      # starting point -> tau
+            for it in range(max_iter):
+                ry = residual(tau.reshape(B, -1).to(x0.dtype)).detach().double().contiguous()
+                # the last call leaves the best iterate in tau
+                _lib.call("dqp_mpc_qp_forward_stepped_bounds", dev, *head, ry, it, it + 1, *tail)
+    ctx.dims, ctx.ws = dims, ws
+    ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
+    ctx.dtype = x0.dtype
+    ctx.save_for_backward(tau, lam, nu, slack, keep[0], keep[2])     # C, F: the stage-wise backward refactors
+    ctx.info, ctx.resid = info, resid
+    return tau.to(x0.dtype)
+
+
+def _mpc_qp_backward(ctx, dtau, flags):
+    """-> [dC, dc, dF, df, dx0] (None where not needed) of a solve _mpc_qp_forward saved: dqp_mpc_qp_backward"""
+    tau, lam, nu, slack, C64, F64 = ctx.saved_tensors
+    dev = tau.device
+    kw = dict(dtype=torch.float64, device=dev)
+    need = ctx.needs_input_grad
+    outs = [torch.empty(s, **kw) if need[i] else None for i, s in enumerate(ctx.shapes)]
+    g = dtau.detach().double().contiguous()
+    opts = _lib.dqp_opts(0.0, 0.0, 0, 0, flags, 0)
+    _lib.call("dqp_mpc_qp_backward", dev, ctx.dims, opts, C64, F64, tau, lam, nu, slack, g, *outs, None, ctx.ws)
+    return [None if o is None else o.to(ctx.dtype) for o in outs]
 
 
 class _MPCQP(Function):
@@ -160,61 +205,14 @@ class _MPCQP(Function):
 
     @staticmethod
     def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T, dyn=None, n_state_host=0):
-        from . import qp as qpmod
-        lib = _lib.load()
-        for t in (C, c, F, f, x0):
-            if not t.is_cuda:
-                raise RuntimeError("diff_qp_mpc_amd.qp_wrapper.MPC runs only on a GPU (HIP); "
-                                   "there is no CPU fallback.")
-        dev, B, nt = x0.device, x0.shape[0], n_state + n_ctrl
-        cv = lambda t: t.detach().double().contiguous()
-        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
-        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl)      # per sample / per knot: names the accepted shapes
         # dyn: a DeviceDynamics whose true step is the equality residual of the iterations (the reference's
         # dyn_res closure, qp_wrapper.py:309,316); F, f stay the linearisation the Newton steps use
-        dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, dyn.id if dyn is not None else 0, n_state_host)
-        batch = qpmod.TERMINATION == "batch"
-        opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, 20, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
-        if dyn is not None:
-            opts.dyn_dt = dyn.dt
-        kw = dict(dtype=torch.float64, device=dev)
-        tau = torch.empty(B, T, nt, **kw)
-        lam = torch.empty(B, 2 * T * n_ctrl, **kw); slack = torch.empty(B, 2 * T * n_ctrl, **kw)
-        nu = torch.empty(B, T * n_state, **kw)
-        info = torch.empty(B, 2, dtype=torch.int32, device=dev)
-        resid = torch.empty(B, **kw)
-        ws = torch.empty(int(lib.dqp_mpc_qp_workspace_bytes(ctypes.byref(dims))) // 8, **kw)
-        tb = int(lib.dqp_mpc_qp_termination_bytes(ctypes.byref(dims), ctypes.byref(opts)))
-        term = torch.empty((tb + 7) // 8, **kw) if tb else None
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_qp_forward_bounds(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep], bl.ref(),
-                                               _ptr(tau), _ptr(lam), _ptr(nu), _ptr(slack), _ptr(info), _ptr(resid),
-                                               _ptr(ws), _ptr(term), _stream(dev))
-        _lib.check(rc, "dqp_mpc_qp_forward_bounds")
-        ctx.dims, ctx.ws = dims, ws
-        ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
-        ctx.dtype = x0.dtype
-        ctx.save_for_backward(tau, lam, nu, slack, keep[0], keep[2])     # C, F: the stage-wise backward refactors
-        ctx.info, ctx.resid = info, resid
-        return tau.to(x0.dtype)
+        dims = _lib.dqp_mpc_dims(x0.shape[0], n_state, n_ctrl, T, 1, dyn.id if dyn is not None else 0, n_state_host)
+        return _mpc_qp_forward(ctx, C, c, F, f, x0, u_lower, u_upper, dims, dyn.dt if dyn is not None else 0.0)
 
     @staticmethod
     def backward(ctx, dtau):
-        lib = _lib.load()
-        tau, lam, nu, slack, C64, F64 = ctx.saved_tensors
-        dev = tau.device
-        kw = dict(dtype=torch.float64, device=dev)
-        need = ctx.needs_input_grad
-        outs = [torch.empty(s, **kw) if need[i] else None for i, s in enumerate(ctx.shapes)]
-        g = dtau.detach().double().contiguous()
-        opts = _lib.dqp_opts(0.0, 0.0, 0, 0, _lib.DQP_FLAG_DENSE_BACKWARD, 0)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_qp_backward(ctypes.byref(ctx.dims), ctypes.byref(opts), _ptr(C64), _ptr(F64), _ptr(tau), _ptr(lam),
-                                         _ptr(nu), _ptr(slack), _ptr(g), *[_ptr(o) for o in outs],
-                                         ctypes.c_void_p(0), _ptr(ctx.ws), _stream(dev))
-        _lib.check(rc, "dqp_mpc_qp_backward")
-        outs = [None if o is None else o.to(ctx.dtype) for o in outs]
-        return (*outs, None, None, None, None, None, None, None)
+        return (*_mpc_qp_backward(ctx, dtau, _lib.DQP_FLAG_DENSE_BACKWARD), None, None, None, None, None, None, None)
 
 
 class _MPCQPStepped(Function):
@@ -243,66 +241,17 @@ class _MPCQPStepped(Function):
 
     @staticmethod
     def forward(ctx, C, c, F, f, x0, u_lower, u_upper, n_state, n_ctrl, T, residual):
-        from . import qp as qpmod
-        lib = _lib.load()
-        dev, B, nt = x0.device, x0.shape[0], n_state + n_ctrl
-        cv = lambda t: t.detach().double().contiguous()
-        keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
-        bl = mpc_bounds_layout(u_lower, u_upper, B, T, n_ctrl)      # per sample / per knot: names the accepted shapes
+        B = x0.shape[0]
         nh = _MPCQPStepped.host_n_state(B, n_state, n_ctrl, T)
         if nh < 0:
             raise NotImplementedError("no stage-wise kernels for (n_state, n_ctrl) = (%d, %d)" % (n_state, n_ctrl))
         dims = _lib.dqp_mpc_dims(B, n_state, n_ctrl, T, 1, 0, nh)
-        batch = qpmod.TERMINATION == "batch"
-        max_iter = 20
-        opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, max_iter, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
-        kw = dict(dtype=torch.float64, device=dev)
-        tau = torch.empty(B, T, nt, **kw)
-        lam = torch.empty(B, 2 * T * n_ctrl, **kw); slack = torch.empty(B, 2 * T * n_ctrl, **kw)
-        nu = torch.empty(B, T * n_state, **kw)
-        info = torch.empty(B, 2, dtype=torch.int32, device=dev)
-        resid = torch.empty(B, **kw)
-        ws = torch.empty(int(lib.dqp_mpc_qp_stepped_workspace_bytes(ctypes.byref(dims))) // 8, **kw)
-        tb = int(lib.dqp_mpc_qp_stepped_termination_bytes(ctypes.byref(dims), ctypes.byref(opts)))
-        term = torch.empty((tb + 7) // 8, **kw) if tb else None
-
-        def call(ry, it0, it1):
-            with torch.cuda.device(dev):
-                rc = lib.dqp_mpc_qp_forward_stepped_bounds(ctypes.byref(dims), ctypes.byref(opts), *[_ptr(t) for t in keep],
-                                                           bl.ref(), _ptr(ry), it0, it1, _ptr(tau), _ptr(lam), _ptr(nu),
-                                                           _ptr(slack), _ptr(info), _ptr(resid), _ptr(ws), _ptr(term),
-                                                           _stream(dev))
-            _lib.check(rc, "dqp_mpc_qp_forward_stepped_bounds")
-
-        with torch.no_grad():
-            call(None, 0, 0)                                    # starting point -> tau
-            for it in range(max_iter):
-                ry = residual(tau.reshape(B, -1).to(x0.dtype)).detach().double().contiguous()
-                call(ry, it, it + 1)                            # the last call leaves the best iterate in tau
-        ctx.dims, ctx.ws = dims, ws
-        ctx.shapes = (C.shape, c.shape, F.shape, f.shape, x0.shape)
-        ctx.dtype = x0.dtype
-        ctx.save_for_backward(tau, lam, nu, slack, keep[0], keep[2])
-        ctx.info, ctx.resid = info, resid
-        return tau.to(x0.dtype)
+        return _mpc_qp_forward(ctx, C, c, F, f, x0, u_lower, u_upper, dims, residual=residual)
 
     @staticmethod
     def backward(ctx, dtau):
-        lib = _lib.load()
-        tau, lam, nu, slack, C64, F64 = ctx.saved_tensors
-        dev = tau.device
-        kw = dict(dtype=torch.float64, device=dev)
-        need = ctx.needs_input_grad
-        outs = [torch.empty(s, **kw) if need[i] else None for i, s in enumerate(ctx.shapes)]
-        g = dtau.detach().double().contiguous()
-        opts = _lib.dqp_opts(0.0, 0.0, 0, 0, _lib.DQP_FLAG_DENSE_BACKWARD | _lib.DQP_FLAG_STAGEWISE, 0)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_qp_backward(ctypes.byref(ctx.dims), ctypes.byref(opts), _ptr(C64), _ptr(F64), _ptr(tau), _ptr(lam),
-                                         _ptr(nu), _ptr(slack), _ptr(g), *[_ptr(o) for o in outs],
-                                         ctypes.c_void_p(0), _ptr(ctx.ws), _stream(dev))
-        _lib.check(rc, "dqp_mpc_qp_backward")
-        outs = [None if o is None else o.to(ctx.dtype) for o in outs]
-        return (*outs, None, None, None, None, None, None)
+        flags = _lib.DQP_FLAG_DENSE_BACKWARD | _lib.DQP_FLAG_STAGEWISE
+        return (*_mpc_qp_backward(ctx, dtau, flags), None, None, None, None, None, None)
 
 
 class _Rollout(Function):
@@ -311,7 +260,6 @@ class _Rollout(Function):
 
     @staticmethod
     def forward(ctx, x0, u, F, f, dyn, n, m, T):
-        lib = _lib.load()
         dev, B = x0.device, x0.shape[0]
         cv = lambda t: t.detach().double().contiguous()
         lin = dyn is None
@@ -320,11 +268,8 @@ class _Rollout(Function):
         x_new, u_new = torch.empty(T, B, n, **kw), torch.empty(T, B, m, **kw)
         alpha, cost_new = torch.empty(B, **kw), torch.empty(B, **kw)
         dims = _lib.dqp_mpc_dims(B, n, m, T, 1, 0)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_line_search(ctypes.byref(dims), 0 if lin else dyn.id, 0.0 if lin else dyn.dt,
-                                         *[_ptr(t) for t in keep], 1.0, 1, _ptr(x_new), _ptr(u_new), _ptr(alpha),
-                                         _ptr(cost_new), _stream(dev))
-        _lib.check(rc, "dqp_mpc_line_search")
+        _lib.call("dqp_mpc_line_search", dev, dims, 0 if lin else dyn.id, 0.0 if lin else dyn.dt, *keep, 1.0, 1,
+                  x_new, u_new, alpha, cost_new)
         ctx.dims, ctx.dyn, ctx.dtype = dims, dyn, x0.dtype
         ctx.shapes = (F.shape if lin else None, f.shape if lin else None)
         ctx.save_for_backward(x_new, u_new, keep[0] if lin else x_new)
@@ -332,7 +277,6 @@ class _Rollout(Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, u, F = ctx.saved_tensors
         dyn, dims = ctx.dyn, ctx.dims
         lin = dyn is None
@@ -344,11 +288,8 @@ class _Rollout(Function):
         d_u = torch.empty(dims.T, dims.nbatch, dims.n_ctrl, **kw) if need[1] else None
         d_F = torch.empty(ctx.shapes[0], **kw) if (lin and need[2]) else None
         d_f = torch.empty(ctx.shapes[1], **kw) if (lin and need[3]) else None
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_rollout_backward(ctypes.byref(dims), 0 if lin else dyn.id, 0.0 if lin else dyn.dt,
-                                              _ptr(F) if lin else ctypes.c_void_p(0), _ptr(x), _ptr(u), _ptr(g64),
-                                              _ptr(d_x0), _ptr(d_u), _ptr(d_F), _ptr(d_f), _stream(dev))
-        _lib.check(rc, "dqp_mpc_rollout_backward")
+        _lib.call("dqp_mpc_rollout_backward", dev, dims, 0 if lin else dyn.id, 0.0 if lin else dyn.dt,
+                  F if lin else None, x, u, g64, d_x0, d_u, d_F, d_f)
         cvt = lambda t: None if t is None else t.to(ctx.dtype)
         return cvt(d_x0), cvt(d_u), cvt(d_F), cvt(d_f), None, None, None, None
 
@@ -448,79 +389,86 @@ class MPC(Module):
     def single_qp(self, x, u, dx, dx_jac, x0, cost, need_cost=True):
         """One QP around (x, u): returns the step (dx, du) to the QP solution and its cost (None with
         need_cost=False: the callers inside this class never read it)."""
+        if isinstance(dx, LinDx):
+            F = dx.F
+            f = dx.f if dx.f is not None else torch.zeros(self.T - 1, self.n_batch, self.n_state,
+                                                          dtype=x0.dtype, device=x0.device)
+        else:
+            F, f = self.linearize_dynamics(x, detach_maybe(u), dx, dx_jac, diff=False)
+        route = self._route(dx)
+        args = (cost.C, cost.c, F, f, x0, *self._bounds(x0.device), self.n_state, self.n_ctrl, self.T)
+        if route.kind == "stepped":
+            # a caller's dynamics module: its residual is evaluated by torch once per PDIPM iteration, the iteration
+            # itself runs on the stage-wise kernels (dqp_mpc_qp_forward_stepped)
+            dx_true = self.dx_true
+            tau = _MPCQPStepped.apply(*args, lambda z: self.dyn_res(z, dx_true, x0))
+        elif route.kind in ("fused", "padded"):
+            # assembly + QP + (in backward) the assembly's adjoint in one kernel each way; with a registered
+            # model the stage-wise kernels evaluate the true-dynamics residual themselves
+            tau = _MPCQP.apply(*args, route.model, route.n_state_host)
+        else:
+            Q, q, G, h, A, b = _AssembleDenseQP.apply(*args)
+            if route.goal_rows:
+                # n_state more equality rows pinning the last state to the goal, which the reference
+                # hard-wires to zero ("b[...] = x0*0 # set to goal", qp_wrapper.py:650-652)
+                n, nt = self.n_state, self.n_state + self.n_ctrl
+                Ag = torch.zeros(self.n_batch, n, self.T * nt, dtype=A.dtype, device=A.device)
+                ar = torch.arange(n, device=A.device)
+                Ag[:, ar, (self.T - 1) * nt + ar] = 1.0
+                A = torch.cat([A, Ag], 1)
+                b = torch.cat([b, torch.zeros(self.n_batch, n, dtype=b.dtype, device=b.device)], 1)
+            # the reference's dyn_res_lam of a registered model, on chip
+            dyn_res = None if route.model is None else DynamicsResidual(route.model, x0, self.T, goal_rows=route.goal_rows)
+            tau = DenseQPFunction()(Q, q, G, h, A, b, dyn_res).to(x0.dtype).reshape(self.n_batch, self.T, -1)
+        x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
+        return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
+
+    def _route(self, dx):
+        """Which path serves a QP of this MPC with dynamics `dx` (and self.dx_true as the true model): host queries only."""
         if self.add_goal_constraint and self.x_goal is not None and bool((torch.as_tensor(self.x_goal) != 0).any()):
             # the reference pins the last state to ZERO in b (qp_wrapper.py:650-652) while its dyn_res
             # subtracts self.x_goal (:339-341): inconsistent unless the goal is zero
             raise NotImplementedError("add_goal_constraint with a nonzero x_goal is inconsistent in the "
                                       "reference (b uses 0, dyn_res uses x_goal); only x_goal = 0 is supported")
-        dyn_res = None
-        stepped = False
+        model, stepped = None, False
         if isinstance(dx, LinDx):
-            F = dx.F
-            f = dx.f if dx.f is not None else torch.zeros(self.T - 1, self.n_batch, self.n_state,
-                                                          dtype=x0.dtype, device=x0.device)
             if not isinstance(self.dx_true, LinDx):
                 raise NotImplementedError("dx_true must be the LinDx itself when dx is a LinDx")
-        else:
-            F, f = self.linearize_dynamics(x, detach_maybe(u), dx, dx_jac, diff=False)
-            if isinstance(self.dx_true, DeviceDynamics):        # the reference's dyn_res_lam, on chip
-                dyn_res = DynamicsResidual(self.dx_true, x0, self.T, goal_rows=self.add_goal_constraint)
-            elif not self.linearised_residual:
-                stepped = True
-        ul = uu = None
-        if self.u_upper is not None:
-            as_t = lambda v: (torch.full((self.n_ctrl,), float(v), dtype=torch.float64, device=x0.device)
-                              if isinstance(v, float) else v.to(x0.device))
-            ul, uu = as_t(self.u_lower), as_t(self.u_upper)
+        elif isinstance(self.dx_true, DeviceDynamics):
+            model = self.dx_true
+        elif not self.linearised_residual:
+            stepped = True
+        size = (self.n_batch, self.n_state, self.n_ctrl, self.T)
+        goal, bounded = bool(self.add_goal_constraint), self.u_upper is not None
         if stepped:
-            # a caller's dynamics module: its residual is evaluated by torch once per PDIPM iteration, the iteration
-            # itself runs on the stage-wise kernels (dqp_mpc_qp_forward_stepped)
-            if (self.add_goal_constraint or ul is None
-                    or _MPCQPStepped.host_n_state(self.n_batch, self.n_state, self.n_ctrl, self.T) < 0):
+            nh = _MPCQPStepped.host_n_state(*size) if bounded and not goal else -1
+            if nh < 0:
                 raise NotImplementedError(
                     "qp_wrapper.MPC with a caller-supplied dynamics module evaluates the module's residual once per "
                     "QP iteration (reference qp_wrapper.py:309,316) around the stage-wise kernels (padded with dummy "
                     "states where (n_state, n_ctrl) has no kernels of its own): that needs control bounds, no goal "
                     "constraint, n_ctrl <= 8 and n_state + n_ctrl <= 32.  "
                     "Register the model (dynamics.DeviceDynamics) or pass linearised_residual=True otherwise.")
-            dx_true = self.dx_true
-            tau = _MPCQPStepped.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T,
-                                      lambda z: self.dyn_res(z, dx_true, x0))
-            x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
-            return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
-        dyn_model = dyn_res.dynamics if isinstance(dyn_res, DynamicsResidual) else None
-        if (FUSED_MPC_QP and (dyn_res is None or dyn_model is not None) and not self.add_goal_constraint
-                and ul is not None
-                and _MPCQP.supported(self.n_batch, self.n_state, self.n_ctrl, self.T, dyn_model)):
-            # assembly + QP + (in backward) the assembly's adjoint in one kernel each way; with a registered
-            # model the stage-wise kernels evaluate the true-dynamics residual themselves
-            tau = _MPCQP.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T, dyn_model)
-            x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
-            return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
+            return Route("stepped", nh)
+        if FUSED_MPC_QP and bounded and not goal and _MPCQP.supported(*size, model):
+            return Route("fused", 0, model)
         nz = self.T * (self.n_state + self.n_ctrl)
-        if (dyn_res is None and not self.add_goal_constraint and ul is not None
+        if (model is None and bounded and not goal
                 and max(nz, 2 * self.T * self.n_ctrl, self.T * self.n_state) > _lib.DQP_MAX_DIM_LARGE):
             # no kernel of its own and too large for the dense route: the stage-wise kernels of the smallest compiled
             # host (n', n_ctrl), the problem padded with n' - n_state dummy states (exact; dqp_mpc_dims.n_state_host)
-            nh = _MPCQP.host_n_state(self.n_batch, self.n_state, self.n_ctrl, self.T)
+            nh = _MPCQP.host_n_state(*size)
             if nh:
-                tau = _MPCQP.apply(cost.C, cost.c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T, None, nh)
-                x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
-                return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
-        Q, q, G, h, A, b = _AssembleDenseQP.apply(cost.C, cost.c, F, f, x0, ul, uu,
-                                                  self.n_state, self.n_ctrl, self.T)
-        if self.add_goal_constraint:
-            # n_state more equality rows pinning the last state to the goal, which the reference
-            # hard-wires to zero ("b[...] = x0*0 # set to goal", qp_wrapper.py:650-652)
-            n, nt = self.n_state, self.n_state + self.n_ctrl
-            Ag = torch.zeros(self.n_batch, n, self.T * nt, dtype=A.dtype, device=A.device)
-            ar = torch.arange(n, device=A.device)
-            Ag[:, ar, (self.T - 1) * nt + ar] = 1.0
-            A = torch.cat([A, Ag], 1)
-            b = torch.cat([b, torch.zeros(self.n_batch, n, dtype=b.dtype, device=b.device)], 1)
-        tau = DenseQPFunction()(Q, q, G, h, A, b, dyn_res).to(x0.dtype).reshape(self.n_batch, self.T, -1)
-        x_qp, u_qp = tau[..., :self.n_state].transpose(0, 1), tau[..., self.n_state:].transpose(0, 1)
-        return x_qp - x, u_qp - u, (self.compute_cost(tau, cost) if need_cost else None)
+                return Route("padded", nh)
+        return Route("dense", 0, model, goal)
+
+    def _bounds(self, dev):
+        """(u_lower, u_upper) as the operators take them: a float becomes an fp64 (n_ctrl,) vector on `dev`"""
+        if self.u_upper is None:
+            return None, None
+        as_t = lambda v: (torch.full((self.n_ctrl,), float(v), dtype=torch.float64, device=dev)
+                          if isinstance(v, float) else v.to(dev))
+        return as_t(self.u_lower), as_t(self.u_upper)
 
     def _damped_step(self, x, u, dx, dx_jac, x0, cost):
         """QP step at (x, u) scaled by the line-search factor (the differentiable last step)."""
@@ -609,7 +557,6 @@ class MPC(Module):
     def _line_search_fused(self, x, u, delta_u, dx, x0, cost):
         """line_search in one launch (dqp_mpc_line_search): rollouts, costs and the per-sample
         backtracking on the device, no host synchronisation."""
-        lib = _lib.load()
         dev, B, T, n, m = x0.device, self.n_batch, self.T, self.n_state, self.n_ctrl
         cv = lambda t: t.detach().double().contiguous()
         lin = isinstance(dx, LinDx)
@@ -619,12 +566,8 @@ class MPC(Module):
         x_new, u_new = torch.empty(T, B, n, **kw), torch.empty(T, B, m, **kw)
         alpha, cost_new = torch.empty(B, **kw), torch.empty(B, **kw)
         dims = _lib.dqp_mpc_dims(B, n, m, T, 1, 0)
-        with torch.cuda.device(dev):
-            rc = lib.dqp_mpc_line_search(ctypes.byref(dims), 0 if lin else dx.id, 0.0 if lin else dx.dt,
-                                         *[_ptr(t) for t in keep], float(self.linesearch_decay),
-                                         int(self.max_linesearch_iter), _ptr(x_new), _ptr(u_new), _ptr(alpha),
-                                         _ptr(cost_new), _stream(dev))
-        _lib.check(rc, "dqp_mpc_line_search")
+        _lib.call("dqp_mpc_line_search", dev, dims, 0 if lin else dx.id, 0.0 if lin else dx.dt, *keep,
+                  float(self.linesearch_decay), int(self.max_linesearch_iter), x_new, u_new, alpha, cost_new)
         dt = x0.dtype
         return x_new.to(dt), u_new.to(dt), alpha.to(dt).reshape(1, B, 1), cost_new.to(dt)
 
@@ -690,11 +633,7 @@ class MPC(Module):
     # ---- the dense assembly as the reference exposes it (qp_wrapper.py:638-679); the solver path itself
     # never materialises these for shapes with a fused MPC QP kernel
     def _dense(self, C, c, F, f, x0):
-        as_t = lambda v: (torch.full((self.n_ctrl,), float(v), dtype=torch.float64, device=x0.device)
-                          if isinstance(v, float) else v.to(x0.device))
-        ul = as_t(self.u_lower) if self.u_lower is not None else None
-        uu = as_t(self.u_upper) if self.u_upper is not None else None
-        return _AssembleDenseQP.apply(C, c, F, f, x0, ul, uu, self.n_state, self.n_ctrl, self.T)
+        return _AssembleDenseQP.apply(C, c, F, f, x0, *self._bounds(x0.device), self.n_state, self.n_ctrl, self.T)
 
     def compute_Qq_dense(self, C, c):
         B = C.shape[1]
@@ -763,6 +702,31 @@ class _GraphReplay(Function):
         return (None,) + tuple(None if gi is None else gi.detach() for gi in g.static_grad_inputs)
 
 
+def _capture_graphs(g, call, sample_inputs, warmup):
+    """Capture `call(*static copies of sample_inputs)` and its backward as the two hipGraphs (one memory pool) that
+    _GraphReplay replays for `g`: warm-up on a side stream, forward graph, backward graph with respect to the inputs
+    that require a gradient.  Sets g.static_inputs / _outputs / _grad_outputs / _grad_inputs, g.fwd_graph, g.bwd_graph."""
+    g.static_inputs = tuple(t.detach().clone().requires_grad_(t.requires_grad) for t in sample_inputs)
+    grad_inputs = tuple(t for t in g.static_inputs if t.requires_grad)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            outs = call(*g.static_inputs)
+            torch.autograd.grad(outs, grad_inputs, tuple(torch.ones_like(o) for o in outs), allow_unused=True)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    pool = torch.cuda.graph_pool_handle()
+    g.fwd_graph, g.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g.fwd_graph, pool=pool):
+        g.static_outputs = call(*g.static_inputs)
+    g.static_grad_outputs = tuple(torch.zeros_like(o) for o in g.static_outputs)
+    with torch.cuda.graph(g.bwd_graph, pool=pool):
+        gi = torch.autograd.grad(g.static_outputs, grad_inputs, g.static_grad_outputs, allow_unused=True)
+    it = iter(gi)
+    g.static_grad_inputs = tuple(next(it) if t.requires_grad else None for t in g.static_inputs)
+
+
 class GraphedMPC:
     """`mpc` (single-QP or SQP mode) captured in two hipGraphs -- forward, and backward through the solver's
     implicit derivative -- sharing one memory pool.  The C-ABI entry points only enqueue on the
@@ -774,29 +738,7 @@ class GraphedMPC:
         if not mpc.single_qp_solve:
             mpc.capturable = True       # SQP: the rounds' stopping test moves onto the device (_solve_nonlin_capturable)
         self.mpc, self.dx_factory = mpc, dx_factory
-        self.static_inputs = tuple(t.detach().clone().requires_grad_(t.requires_grad) for t in sample_inputs)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                outs = self._call(*self.static_inputs)
-                torch.autograd.grad(outs, self._grad_inputs(), tuple(torch.ones_like(o) for o in outs),
-                                    allow_unused=True)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
-        self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.fwd_graph, pool=pool):
-            self.static_outputs = self._call(*self.static_inputs)
-        self.static_grad_outputs = tuple(torch.zeros_like(o) for o in self.static_outputs)
-        with torch.cuda.graph(self.bwd_graph, pool=pool):
-            gi = torch.autograd.grad(self.static_outputs, self._grad_inputs(), self.static_grad_outputs,
-                                     allow_unused=True)
-        it = iter(gi)
-        self.static_grad_inputs = tuple(next(it) if t.requires_grad else None for t in self.static_inputs)
-
-    def _grad_inputs(self):
-        return tuple(t for t in self.static_inputs if t.requires_grad)
+        _capture_graphs(self, self._call, sample_inputs, warmup)
 
     def _call(self, *args):
         if self.dx_factory is None:
