@@ -12,7 +12,10 @@ What runs where:
   * the QP itself (qp.DenseQPFunction, qp_wrapper.py:316): fused HIP PDIPM (csrc/dqp_*.hip);
   * the SQP outer loop, rollout, cost and line search (behaviour of qp_wrapper.py:298-436,
     598-611, 690-692): vectorised torch ops on the same device (they call user-supplied Python
-    dynamics, which cannot be fused).
+    dynamics, which cannot be fused);
+  * with ONE_CALL_SQP (off by default) and a registered device model, the gradient-free rounds of that loop as
+    dqp_mpc_sqp_rounds calls (csrc/dqp_mpc_sqp.hip): linearisation, QP, line search, keep-best and the stop test on the
+    device, one host read per round.
 
 The reference passes the TRUE-dynamics residual closure into the PDIPM (`dyn_res_lam`,
 qp_wrapper.py:309,316).  Here: for LinDx that residual IS A z - b (what the kernels evaluate); for
@@ -63,6 +66,12 @@ class LinDx(NamedTuple):
 FUSED_MPC_QP = True
 # line_search (rollouts + costs + backtracking) as one kernel for LinDx / registered device models
 FUSED_LINE_SEARCH = True
+# solve_nonlin's gradient-free rounds of a registered device model through dqp_mpc_sqp_rounds (linearisation, QP, line
+# search, keep-best and the stop test enqueued by one call, MPC._sqp_on_device says where); False: the Python loop
+ONE_CALL_SQP = False
+# rounds enqueued per dqp_mpc_sqp_rounds call, with one host read of the stop flag behind each call; 1 never runs a QP
+# the Python loop would not have run
+SQP_CHECK_EVERY = 1
 
 # member names and values as in qpth.qp_wrapper.GradMethods
 GradMethods = Enum("GradMethods", ["AUTO_DIFF", "FINITE_DIFF", "ANALYTIC", "ANALYTIC_CHECK"])
@@ -126,6 +135,15 @@ class _AssembleDenseQP(Function):
         return (*outs, None, None, None, None, None)
 
 
+def _mpc_qp_opts(dyn_dt=0.0, max_iter=20):
+    """The dqp_opts of an MPC QP solve: eps 1e-12, max_iter 20 and not_improved_lim 3 as the reference calls its solver,
+    the termination mode of qp.TERMINATION, `dyn_dt` the step of a registered model."""
+    batch = qpmod.TERMINATION == "batch"
+    opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, max_iter, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
+    opts.dyn_dt = dyn_dt
+    return opts
+
+
 def _mpc_qp_forward(ctx, C, c, F, f, x0, u_lower, u_upper, dims, dyn_dt=0.0, residual=None):
     """The forward of _MPCQP (one dqp_mpc_qp_forward_bounds call) and, with `residual`, of _MPCQPStepped (one
     dqp_mpc_qp_forward_stepped_bounds call per PDIPM iteration, the caller's residual evaluated on the iterate in
@@ -136,9 +154,7 @@ def _mpc_qp_forward(ctx, C, c, F, f, x0, u_lower, u_upper, dims, dyn_dt=0.0, res
     keep = [cv(C), cv(c), cv(F), cv(f), cv(x0)]
     bl = mpc_bounds_layout(u_lower, u_upper, B, T, m)      # per sample / per knot: names the accepted shapes
     max_iter = 20
-    batch = qpmod.TERMINATION == "batch"
-    opts = _lib.dqp_opts(1e-12, qpmod.STALL_TOL, max_iter, 3, (_lib.DQP_FLAG_BATCH_TERMINATION if batch else 0) | EXTRA_FLAGS, 0)
-    opts.dyn_dt = dyn_dt
+    opts = _mpc_qp_opts(dyn_dt, max_iter)
     kw = dict(dtype=torch.float64, device=dev)
     tau = torch.empty(B, T, n + m, **kw)
     lam = torch.empty(B, 2 * T * m, **kw); slack = torch.empty(B, 2 * T * m, **kw)
@@ -485,6 +501,8 @@ class MPC(Module):
         differentiable step from that trajectory."""
         keep_x = keep_u = keep_cost = None
         stalls = 0          # the reference never increments this counter either (qp_wrapper.py:356-380)
+        if self.qp_iter >= 1 and self._sqp_on_device(dx, dx_jac, cost, x0):
+            return self._solve_nonlin_device(x, u, dx, dx_jac, x0, cost)
         if getattr(self, "capturable", False):
             return self._solve_nonlin_capturable(x, u, dx, dx_jac, x0, cost)
         with torch.no_grad():
@@ -504,6 +522,61 @@ class MPC(Module):
                 if (u - u_before).norm() < self.eps or stalls > self.not_improved_lim:
                     break
         return self._damped_step(keep_x, keep_u, dx, dx_jac, x0, cost)
+
+    def _sqp_on_device(self, dx, dx_jac, cost, x0=None):
+        """Does solve_nonlin run its gradient-free rounds through dqp_mpc_sqp_rounds?  Host queries only.  ONE_CALL_SQP is
+        on, the cost is a QuadCost with a batched C, `dx` is a registered model that is also the true model, `dx_jac` is
+        that model's own `jac` (the kernels linearise with the registry's templates: any other callable keeps the Python
+        loop, which calls it), the Jacobians are read from dx_jac (ANALYTIC / AUTO_DIFF), the QP takes the fused route with
+        the model and the library serves the shape.  `x0`, where given, must live on the GPU: solve_nonlin passes it; it
+        is optional so that the other conditions can be asked for (and tested) on a host without a device, like _route.
+        "Its own `jac`" is checked on both halves of the bound method (`__self__` is the model, `__func__` is
+        DeviceDynamics.jac): another method of the model bound as dx_jac is a caller's callable too."""
+        if not ONE_CALL_SQP or (x0 is not None and not x0.is_cuda):
+            return False
+        if not (isinstance(cost, QuadCost) and torch.is_tensor(cost.C) and cost.C.dim() == 4):
+            return False
+        if not isinstance(dx, DeviceDynamics) or self.dx_true is not dx or getattr(dx_jac, "__self__", None) is not dx:
+            return False
+        if getattr(dx_jac, "__func__", None) is not DeviceDynamics.jac:
+            return False
+        if self.grad_method not in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF):
+            return False
+        route = self._route(dx)
+        if route.kind != "fused" or route.model is not dx:
+            return False
+        dims = _lib.dqp_mpc_dims(self.n_batch, self.n_state, self.n_ctrl, self.T, 1, dx.id)
+        return bool(_lib.load().dqp_mpc_sqp_supported(ctypes.byref(dims)))
+
+    def _solve_nonlin_device(self, x, u, dx, dx_jac, x0, cost):
+        """solve_nonlin where _sqp_on_device holds: the rounds as dqp_mpc_sqp_rounds calls of SQP_CHECK_EVERY rounds, the
+        stop flag read once behind each call (`capturable`: every round in one call, nothing read -- rounds behind the
+        stop change nothing), then the differentiable step from the best trajectory, as in the Python loop."""
+        dev, B, T, n, m = x0.device, self.n_batch, self.T, self.n_state, self.n_ctrl
+        kw = dict(dtype=torch.float64, device=dev)
+        cv = lambda t: t.detach().double().contiguous()
+        C64, c64, x064 = cv(cost.C), cv(cost.c), cv(x0)
+        xs, us = torch.empty(T, B, n, **kw).copy_(x.detach()), torch.empty(T, B, m, **kw).copy_(u.detach())   # in/out: own copies
+        keep_x, keep_u, keep_cost = torch.empty(T, B, n, **kw), torch.empty(T, B, m, **kw), torch.empty(B, **kw)
+        state = torch.empty(4, dtype=torch.int32, device=dev)
+        bl = mpc_bounds_layout(*self._bounds(dev), B, T, m)
+        dims = _lib.dqp_mpc_dims(B, n, m, T, 1, dx.id)
+        opts = _mpc_qp_opts(dx.dt)
+        ws = torch.empty(int(_lib.load().dqp_mpc_sqp_workspace_bytes(ctypes.byref(dims), ctypes.byref(opts))) // 8, **kw)
+        rounds = lambda begin, end: _lib.call(
+            "dqp_mpc_sqp_rounds", dev, dims, opts, C64, c64, x064, bl.ref(), float(self.linesearch_decay),
+            int(self.max_linesearch_iter), float(self.best_cost_eps), float(self.eps), begin, end, xs, us, keep_x, keep_u,
+            keep_cost, state, ws)
+        if getattr(self, "capturable", False):
+            rounds(0, self.qp_iter)
+        else:
+            every = max(1, int(SQP_CHECK_EVERY))
+            for begin in range(0, self.qp_iter, every):
+                rounds(begin, min(begin + every, self.qp_iter))
+                if bool(state[0]):
+                    break
+        dt = x0.dtype
+        return self._damped_step(keep_x.to(dt), keep_u.to(dt), dx, dx_jac, x0, cost)
 
     def _solve_nonlin_capturable(self, x, u, dx, dx_jac, x0, cost):
         """solve_nonlin without its host test (the `break` on |u - u_before| < eps, qp_wrapper.py:392): every one of the

@@ -30,7 +30,9 @@ extern "C" {
 
 #define DQP_VERSION 303 /* (additive at 303, no bump: dqp_qp_backward_shared_bytes / dqp_qp_backward_shared -- gradients of
                            shared parameters summed over the batch on the device; dqp_al_mpc_solve_fused_supported /
-                           dqp_al_mpc_solve_fused_bytes / dqp_al_mpc_solve_fused -- dqp_al_mpc_solve as one launch;)
+                           dqp_al_mpc_solve_fused_bytes / dqp_al_mpc_solve_fused -- dqp_al_mpc_solve as one launch;
+                           dqp_mpc_linearize, dqp_mpc_sqp_supported / _workspace_bytes / _rounds -- the SQP rounds of
+                           qp_wrapper.MPC for a registered model, enqueued by one call;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -710,6 +712,67 @@ int dqp_mpc_qp_forward_stepped_bounds(const dqp_mpc_dims *dims, const dqp_opts *
                                       const double *ext_ry, int32_t it_begin, int32_t it_end, double *tau, double *lam,
                                       double *nu, double *slack, int32_t *info, double *best_resid, void *workspace,
                                       void *termination, void *stream);
+
+/*
+ * The gradient-free SQP rounds of qp_wrapper.MPC.solve_nonlin for a registered device model (additive at 303;
+ * csrc/dqp_mpc_sqp.hip).  Replaces, per round of qpth/qp_wrapper.py:348-414: linearize_dynamics (:481-515), single_qp,
+ * line_search, the best-trajectory bookkeeping and the loop's two host tests.  The differentiable last step stays with
+ * the caller.
+ *
+ * dqp_mpc_linearize: F_t = [df/dx, df/du](x_t, u_t), f_t = step(x_t, u_t) - F_t [x_t; u_t], t < T-1, of the model
+ * dims->dyn_id (sizes as in dims, else DQP_ERR_BAD_ARG), in the layouts dqp_mpc_qp_forward reads: x (T,B,n), u (T,B,m) ->
+ * F (T-1,B,n,nt), f (T-1,B,n).  One launch; forward-mode duals of the registry's templates, as dqp_dyn_jacobian.  Reads
+ * neither has_bounds nor n_state_host.
+ *
+ * dqp_mpc_sqp_rounds enqueues rounds round_begin .. round_end-1 of the loop.  dims->dyn_id names the model, `opts` is what
+ * dqp_mpc_qp_forward takes with dyn_dt the model's step (> 0); C (T,B,nt,nt), c (T,B,nt), x0 (B,n) and the bounds as for
+ * dqp_mpc_qp_forward_bounds; decay, max_linesearch_iter as for dqp_mpc_line_search.  All state between calls lives in the
+ * caller's buffers: x (T,B,n), u (T,B,m) the current trajectory (in/out), keep_x, keep_u, keep_cost (B) the best
+ * trajectory seen per sample, and state, int32[4] = {done, rounds applied, 0, 0}.  A call with round_begin == 0 resets
+ * `state` on the device (round 0 ignores what it finds there and leaves {done, 1, 0, 0}; an empty range from 0 leaves
+ * zeros), and round 0 stores keep_* unconditionally.  One round:
+ *   1. F, f <- the linearisation at (x, u);
+ *   2. tau <- dqp_mpc_qp_forward_bounds (the model's true step in the equality residual);
+ *   3. du = tau_u - u;
+ *   4. x_new, u_new, cost_new <- dqp_mpc_line_search from x0;
+ *   5. per sample: cost_new <= keep_cost + best_cost_eps (or round 0) -> keep_x, keep_u, keep_cost <- the new ones;
+ *   6. x, u <- x_new, u_new;
+ *   7. done |= |u_new - u|_F < eps over the whole batch (qp_wrapper.py:392); rounds applied += 1.
+ * A round that starts with `done` set changes nothing in x, u, keep_* or state (its QP and line search run on the
+ * previous round's F, f and write only the workspace): enqueueing every round in one call equals the reference's `break`.
+ * The batch-wide sum of step 7 crosses workgroups at launch boundaries only and is added in index order (64 samples per
+ * partial, then the partials): no atomics, the same bits from run to run.  Four launches per round on top of the QP's and
+ * the line search's.  Only enqueues: no synchronisation, no allocation, no copy to the host (capturable).
+ *
+ * dqp_mpc_sqp_supported: 1 iff dims->dyn_id is a registered model of the sizes in dims, has_bounds is set,
+ * n_state_host == 0, dqp_mpc_qp_supported(dims) == 1 and the line search serves the size (n_state <= 12, n_ctrl <= 8).
+ * Needs no device.
+ *
+ * dqp_mpc_sqp_workspace_bytes, with B = nbatch, n = n_state, m = n_ctrl, nt = n + m and ev(x) = x rounded up to even --
+ * every array starts on 16 bytes of a 16-byte aligned workspace -- (0 when unsupported, nbatch <= 0 or opts == NULL):
+ *     8 * (ev((T-1) B n nt) + ev((T-1) B n)            F, f
+ *          + ev(B T nt) + 4 B T m + ev(B T n)          tau, lam, slack, nu
+ *          + 2 ev(B)                                   info (B,2) int32, best_resid
+ *          + 2 ev(T B m) + ev(T B n)                   du, u_new, x_new
+ *          + 2 ev(B) + ev(ceil(B / 64)))               alpha, cost_new, the partial sums
+ *     + 16 * ceil(dqp_mpc_qp_workspace_bytes(dims) / 16) + 16 * ceil(dqp_mpc_qp_termination_bytes(dims, opts) / 16)
+ *
+ * Return codes: DQP_ERR_BAD_ARG for a null dims / opts / bounds, an unknown model or one whose sizes differ from dims,
+ * has_bounds == 0, n_state_host != 0 and a bounds layout dqp_mpc_qp_forward_bounds refuses; DQP_ERR_TOO_LARGE where
+ * dqp_mpc_sqp_supported is 0 otherwise; then nbatch == 0 returns DQP_OK with nothing enqueued; then DQP_ERR_BAD_ARG for a
+ * null array, round_begin < 0, round_end < round_begin, max_linesearch_iter < 1 or dyn_dt <= 0.
+ */
+int dqp_mpc_linearize(const dqp_mpc_dims *dims, double dt, const double *x, const double *u,
+                      double *F, double *f, void *stream);
+
+int    dqp_mpc_sqp_supported(const dqp_mpc_dims *dims);
+size_t dqp_mpc_sqp_workspace_bytes(const dqp_mpc_dims *dims, const dqp_opts *opts);
+int    dqp_mpc_sqp_rounds(const dqp_mpc_dims *dims, const dqp_opts *opts, const double *C, const double *c,
+                          const double *x0, const dqp_mpc_bounds *bounds, double decay,
+                          int32_t max_linesearch_iter, double best_cost_eps, double eps,
+                          int32_t round_begin, int32_t round_end, double *x, double *u,
+                          double *keep_x, double *keep_u, double *keep_cost, int32_t *state,
+                          void *workspace, void *stream);
 
 /* ----------------------------------------------------------------- device dynamics registry */
 
