@@ -47,9 +47,6 @@ DQP_MAX_DIM = 64
 DQP_MAX_DIM_LARGE = 512
 SHARED_GRAD_KC = 64      # samples per split-K chunk of dqp_qp_backward_shared (csrc/dqp_shared_grad.hip: KC)
 
-DQP_DYN = {"pendulum1l": 1, "cartpole1l": 2, "cartpole2l": 3, "pendulum_euler": 4, "pendulum_dx": 5,
-           "rexquadrotor": 6, "integrator": 7}
-
 
 class dqp_al_mpc_dims(ctypes.Structure):
     _fields_ = [("nbatch", ctypes.c_int32), ("n_state", ctypes.c_int32), ("n_ctrl", ctypes.c_int32),
@@ -112,8 +109,16 @@ def prototypes(header):
     return out
 
 
+def dyn_ids(header):
+    """{"pendulum1l": 1, ...}: the `DQP_DYN_NAME = k` enumerators in the text of include/dqp.h, lower-cased without the prefix"""
+    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    return {name.lower(): int(k) for name, k in re.findall(r"\bDQP_DYN_([A-Z0-9_]+)\s*=\s*(\d+)", text)}
+
+
 with open(os.path.join(os.path.dirname(_build.HERE), "include", "dqp.h")) as _f:
-    PROTOTYPES = prototypes(_f.read())
+    _header = _f.read()
+PROTOTYPES = prototypes(_header)
+DQP_DYN = dyn_ids(_header)       # the registered device models; load() checks that the library knows each
 SYMBOLS = tuple(PROTOTYPES)      # every symbol include/dqp.h declares
 _launches = {}                   # the entries call() serves (last parameter `stream`), filled by load()
 _lib = None
@@ -146,6 +151,10 @@ def load():
         fn.restype, fn.argtypes = restype, argtypes
         if params and params[-1] == "stream":
             _launches[name] = fn
+    for name, k in DQP_DYN.items():
+        if lib.dqp_dyn_sizes(k, None, None) != DQP_OK:
+            raise RuntimeError("diff_qp_mpc_amd: include/dqp.h declares DQP_DYN_%s = %d, which %s does not register"
+                               % (name.upper(), k, so))
     _lib = lib
     return lib
 

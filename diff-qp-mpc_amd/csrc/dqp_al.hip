@@ -922,16 +922,9 @@ template <class Model> int launch_ls_layout(const LsAPS &P, hipStream_t st)
 
 int launch_ls(const LsAPS &P, hipStream_t st)
 {
-    switch (P.dyn) {
-    case DQP_DYN_PENDULUM1L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>(P, st);
-    case DQP_DYN_CARTPOLE1L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>(P, st);
-    case DQP_DYN_CARTPOLE2L: return launch_ls_layout<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>(P, st);
-    case DQP_DYN_PENDULUM_EULER: return launch_ls_layout<dqp::dyn::PendulumEuler>(P, st);
-    case DQP_DYN_PENDULUM_DX: return launch_ls_layout<dqp::dyn::PendulumDx>(P, st);
-    case DQP_DYN_REXQUADROTOR: return launch_ls_layout<dqp::dyn::RexQuadrotor>(P, st);
-    case DQP_DYN_INTEGRATOR: return launch_ls_layout<dqp::dyn::Integrator>(P, st);
-    default: return DQP_ERR_BAD_ARG;
-    }
+    return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
+        return launch_ls_layout<typename decltype(model)::Map>(P, st);
+    });
 }
 
 struct OutP {
@@ -1053,30 +1046,12 @@ __global__ __launch_bounds__(256) void al_start_kernel(StartP P)
 int launch_outer(const OutP &P, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.B + 15) / 16)), block(256);
-    if (P.bsb != 0 || P.bst != 0) {
-        switch (P.dyn) {
-        case DQP_DYN_PENDULUM1L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>>, grid, block, 0, st, P); break;
-        case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>>, grid, block, 0, st, P); break;
-        case DQP_DYN_CARTPOLE2L: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>>, grid, block, 0, st, P); break;
-        case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::PendulumEuler>>, grid, block, 0, st, P); break;
-        case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::PendulumDx>>, grid, block, 0, st, P); break;
-        case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::RexQuadrotor>>, grid, block, 0, st, P); break;
-        case DQP_DYN_INTEGRATOR: DQP_LAUNCH(al_outer_kernel<StridedBounds<dqp::dyn::Integrator>>, grid, block, 0, st, P); break;
-        default: return DQP_ERR_BAD_ARG;
-        }
+    return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
+        using Map = typename decltype(model)::Map;
+        if (P.bsb != 0 || P.bst != 0) DQP_LAUNCH(al_outer_kernel<StridedBounds<Map>>, grid, block, 0, st, P);
+        else DQP_LAUNCH(al_outer_kernel<Map>, grid, block, 0, st, P);
         return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-    }
-    switch (P.dyn) {
-    case DQP_DYN_PENDULUM1L: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE2L: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(al_outer_kernel<dqp::dyn::PendulumEuler>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(al_outer_kernel<dqp::dyn::PendulumDx>, grid, block, 0, st, P); break;
-    case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(al_outer_kernel<dqp::dyn::RexQuadrotor>, grid, block, 0, st, P); break;
-    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(al_outer_kernel<dqp::dyn::Integrator>, grid, block, 0, st, P); break;
-    default: return DQP_ERR_BAD_ARG;
-    }
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    });
 }
 
 struct SelP {
@@ -1263,8 +1238,7 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || n_steps < 1) return DQP_ERR_BAD_ARG;
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
-    int32_t dn = 0, dm = 0;
-    if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     const long long bsb = bounds->stride_b, bst = bounds->stride_t;
     if (!x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !xu || !fail || !workspace) return DQP_ERR_BAD_ARG;
@@ -1371,8 +1345,7 @@ dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, cons
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
     const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     if (d->nbatch == 0) return DQP_OK;
-    int32_t dn = 0, dm = 0;
-    if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     if (d->n_state > 12 || d->n_state + d->n_ctrl > 16) return DQP_ERR_TOO_LARGE;
     if (!xu || !x0 || !lam || !rho || !Qdiag || !q || !u_lower || !u_upper || !lam_new || !cost || !res_norm)
         return DQP_ERR_BAD_ARG;

@@ -960,23 +960,16 @@ int dqp::al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id,
                                            void *stream, int keep)
 {
     if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    int32_t n = 0, m = 0;
-    if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
     if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !update || !factor)
         return DQP_ERR_BAD_ARG;
     BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, nullptr, nullptr, nullptr, update,
                (double *)factor, info, dt, d->nbatch, d->T, keep, (long long)bounds->stride_b, (long long)bounds->stride_t};
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return run_newton_layout<Robot<Pendulum1l>>(P, stream);
-    case DQP_DYN_CARTPOLE1L: return run_newton_layout<Robot<Cartpole1l>>(P, stream);
-    case DQP_DYN_CARTPOLE2L: return run_newton_layout<Robot<Cartpole2l>>(P, stream);
-    case DQP_DYN_PENDULUM_EULER: return run_newton_layout<PendulumEuler>(P, stream);
-    case DQP_DYN_REXQUADROTOR: return run_newton_layout<RexQuadrotor>(P, stream);
-    case DQP_DYN_INTEGRATOR: return run_newton_layout<Integrator>(P, stream);
-    default: return run_newton_layout<PendulumDx>(P, stream);
-    }
+    return visit<int>(dyn_id, DQP_ERR_BAD_ARG, [&](auto model) {
+        return run_newton_layout<typename decltype(model)::Map>(P, stream);
+    });
 }
 
 int dqp::al_banded_newton_step_keep(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
@@ -1015,8 +1008,7 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
                     void *stream)
 {
     if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    int32_t n = 0, m = 0;
-    if (dyn_id != 0 && (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl)) return DQP_ERR_BAD_ARG;
+    if (dyn_id != 0 && !dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
     if (!factor || !rhs || !out) return DQP_ERR_BAD_ARG;
     BandP P = {};
@@ -1027,15 +1019,9 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
 #undef X
         return dqp::al_banded_wide_solve(d->n_state, d->n_ctrl, &P, sizeof(P), stream);
     }
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return run_solve<Robot<Pendulum1l>>(P, stream);
-    case DQP_DYN_CARTPOLE1L: return run_solve<Robot<Cartpole1l>>(P, stream);
-    case DQP_DYN_CARTPOLE2L: return run_solve<Robot<Cartpole2l>>(P, stream);
-    case DQP_DYN_PENDULUM_EULER: return run_solve<PendulumEuler>(P, stream);
-    case DQP_DYN_REXQUADROTOR: return run_solve<RexQuadrotor>(P, stream);
-    case DQP_DYN_INTEGRATOR: return run_solve<Integrator>(P, stream);
-    default: return run_solve<PendulumDx>(P, stream);
-    }
+    return visit<int>(dyn_id, DQP_ERR_BAD_ARG, [&](auto model) {
+        return run_solve<typename decltype(model)::Map>(P, stream);
+    });
 }
 
 /*

@@ -432,23 +432,17 @@ template <class Map> size_t fused_lds_bytes(int T, bool strided)
 
 size_t fused_lds(int dyn_id, int T, bool strided = false)
 {
-    using namespace dqp::dyn;
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return fused_lds_bytes<Robot<Pendulum1l>>(T, strided);
-    case DQP_DYN_CARTPOLE1L: return fused_lds_bytes<Robot<Cartpole1l>>(T, strided);
-    case DQP_DYN_CARTPOLE2L: return fused_lds_bytes<Robot<Cartpole2l>>(T, strided);
-    case DQP_DYN_PENDULUM_EULER: return fused_lds_bytes<PendulumEuler>(T, strided);
-    case DQP_DYN_PENDULUM_DX: return fused_lds_bytes<PendulumDx>(T, strided);
-    case DQP_DYN_INTEGRATOR: return fused_lds_bytes<Integrator>(T, strided);
-    default: return 0;
-    }
+    return dqp::dyn::visit<size_t>(dyn_id, 0, [&](auto model) -> size_t {
+        using Map = typename decltype(model)::Map;
+        if constexpr (Map::NX + Map::NU <= FG) return fused_lds_bytes<Map>(T, strided);
+        else return 0;          // the knot does not fit a group's tile
+    });
 }
 
 bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id, bool strided = false)
 {
     if (!d || d->T < 2 || d->T > 32 || d->nbatch < 0) return false;
-    int32_t n = 0, m = 0;
-    if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl || n + m > FG) return false;
+    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl) || d->n_state + d->n_ctrl > FG) return false;
     const size_t lds = fused_lds(dyn_id, d->T, strided);
     return lds > 0 && lds + FUSED_STATIC_LDS <= FUSED_LDS_LIMIT;
 }
@@ -536,8 +530,7 @@ dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, i
         !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
         return DQP_ERR_BAD_ARG;
     if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
-    int32_t dn = 0, dm = 0;
-    if (dqp_dyn_sizes(dyn_id, &dn, &dm) != DQP_OK || dn != d->n_state || dm != d->n_ctrl) return DQP_ERR_BAD_ARG;
+    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     if (!fused_ok(d, dyn_id, strided)) return DQP_ERR_TOO_LARGE;
     hipStream_t st = (hipStream_t)stream;
     // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
@@ -546,15 +539,11 @@ dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, i
                         xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, dt, d->nbatch, d->T, al_iter,
                         newton_steps, n_prev}, (long long)bounds->stride_b, (long long)bounds->stride_t};
     const size_t lds = fused_lds(dyn_id, d->T, strided);
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return launch_fused<Robot<Pendulum1l>>(P, lds, st);
-    case DQP_DYN_CARTPOLE1L: return launch_fused<Robot<Cartpole1l>>(P, lds, st);
-    case DQP_DYN_CARTPOLE2L: return launch_fused<Robot<Cartpole2l>>(P, lds, st);
-    case DQP_DYN_PENDULUM_EULER: return launch_fused<PendulumEuler>(P, lds, st);
-    case DQP_DYN_PENDULUM_DX: return launch_fused<PendulumDx>(P, lds, st);
-    case DQP_DYN_INTEGRATOR: return launch_fused<Integrator>(P, lds, st);
-    default: return DQP_ERR_TOO_LARGE;
-    }
+    return visit<int>(dyn_id, DQP_ERR_TOO_LARGE, [&](auto model) -> int {
+        using Map = typename decltype(model)::Map;
+        if constexpr (Map::NX + Map::NU <= FG) return launch_fused<Map>(P, lds, st);
+        else return DQP_ERR_TOO_LARGE;
+    });
 }
 
 }  // extern "C"

@@ -168,20 +168,12 @@ extern "C" {
 
 __attribute__((visibility("default"))) int dqp_dyn_sizes(int id, int32_t *n_state, int32_t *n_ctrl)
 {
-    int n, m = 1;
-    switch (id) {
-    case DQP_DYN_PENDULUM1L: n = 2; break;
-    case DQP_DYN_CARTPOLE1L: n = 4; break;
-    case DQP_DYN_CARTPOLE2L: n = 6; break;
-    case DQP_DYN_PENDULUM_EULER: n = 2; break;
-    case DQP_DYN_PENDULUM_DX: n = 3; break;
-    case DQP_DYN_REXQUADROTOR: n = 12; m = 4; break;
-    case DQP_DYN_INTEGRATOR: n = 2; break;
-    default: return DQP_ERR_BAD_ARG;
-    }
-    if (n_state) *n_state = n;
-    if (n_ctrl) *n_ctrl = m;
-    return DQP_OK;
+    return visit<int>(id, DQP_ERR_BAD_ARG, [&](auto model) {
+        using Map = typename decltype(model)::Map;
+        if (n_state) *n_state = Map::NX;
+        if (n_ctrl) *n_ctrl = Map::NU;
+        return DQP_OK;
+    });
 }
 
 __attribute__((visibility("default"))) int dqp_dyn_step(int id, int32_t n, const double *x, const double *u,
@@ -191,15 +183,9 @@ __attribute__((visibility("default"))) int dqp_dyn_step(int id, int32_t n, const
     if (dqp_dyn_sizes(id, nullptr, nullptr) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (n == 0) return DQP_OK;
     if (!x || !u || !x_next) return DQP_ERR_BAD_ARG;
-    switch (id) {
-    case DQP_DYN_PENDULUM1L: return run_step<Robot<Pendulum1l>>(n, x, u, dt, x_next, stream);
-    case DQP_DYN_CARTPOLE1L: return run_step<Robot<Cartpole1l>>(n, x, u, dt, x_next, stream);
-    case DQP_DYN_CARTPOLE2L: return run_step<Robot<Cartpole2l>>(n, x, u, dt, x_next, stream);
-    case DQP_DYN_PENDULUM_EULER: return run_step<PendulumEuler>(n, x, u, dt, x_next, stream);
-    case DQP_DYN_REXQUADROTOR: return run_step<RexQuadrotor>(n, x, u, dt, x_next, stream);
-    case DQP_DYN_INTEGRATOR: return run_step<Integrator>(n, x, u, dt, x_next, stream);
-    default: return run_step<PendulumDx>(n, x, u, dt, x_next, stream);
-    }
+    return visit<int>(id, DQP_ERR_BAD_ARG, [&](auto model) {
+        return run_step<typename decltype(model)::Map>(n, x, u, dt, x_next, stream);
+    });
 }
 
 __attribute__((visibility("default"))) int dqp_dyn_jacobian(int id, int32_t n, const double *x, const double *u,
@@ -210,15 +196,10 @@ __attribute__((visibility("default"))) int dqp_dyn_jacobian(int id, int32_t n, c
     if (dqp_dyn_sizes(id, nullptr, nullptr) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (n == 0) return DQP_OK;
     if (!x || !u) return DQP_ERR_BAD_ARG;
-    switch (id) {
-    case DQP_DYN_PENDULUM1L: return run_jac<Robot<Pendulum1l>, 3>(n, x, u, dt, x_next, Jx, Ju, stream);
-    case DQP_DYN_CARTPOLE1L: return run_jac<Robot<Cartpole1l>, 5>(n, x, u, dt, x_next, Jx, Ju, stream);
-    case DQP_DYN_CARTPOLE2L: return run_jac<Robot<Cartpole2l>, 4>(n, x, u, dt, x_next, Jx, Ju, stream);
-    case DQP_DYN_PENDULUM_EULER: return run_jac<PendulumEuler, 3>(n, x, u, dt, x_next, Jx, Ju, stream);
-    case DQP_DYN_REXQUADROTOR: return run_jac<RexQuadrotor, 2>(n, x, u, dt, x_next, Jx, Ju, stream);
-    case DQP_DYN_INTEGRATOR: return run_jac<Integrator, 3>(n, x, u, dt, x_next, Jx, Ju, stream);
-    default: return run_jac<PendulumDx, 4>(n, x, u, dt, x_next, Jx, Ju, stream);
-    }
+    return visit<int>(id, DQP_ERR_BAD_ARG, [&](auto model) {
+        using M = decltype(model);
+        return run_jac<typename M::Map, M::KC>(n, x, u, dt, x_next, Jx, Ju, stream);
+    });
 }
 
 __attribute__((visibility("default"))) int dqp_dyn_forward_dynamics(int id, int32_t n, const double *q,

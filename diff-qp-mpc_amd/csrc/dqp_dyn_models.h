@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "../../include/dqp.h"      // DQP_DYN_*
+
 namespace dqp {
 namespace dyn {
 
@@ -353,6 +355,46 @@ struct RexQuadrotor {
         for (int i = 0; i < NX; ++i) xn[i] = x[i] + (dt / 6.0) * (acc[i] + k[i]);
     }
 };
+
+// ------------------------------------------------------------------ the registered models
+// One row per model: (id of include/dqp.h, state-space map, KC).  KC is the number of forward-mode directions one pass
+// of the model's Jacobian carries (dqp_dyn.hip: jac_kernel, dqp_mpc_sqp.hip: linearize_kernel), chosen per model for
+// its register demand.  Every entry that takes a dyn_id reaches the model's type through visit() below, on the host and
+// in the kernels (dqp_pdipm.hip true_dyn_res, dqp_ric_kernels.h model_residuals).
+// Places that also enumerate the models, each with its own switch:
+//   dqp_al.hip al_linearize_kernel: its instruction stream changes when it goes through visit() (its default is a model);
+//   dqp_dyn.hip dqp_dyn_forward_dynamics / _derivatives: the three Robot<> inner models, not the maps of this list.
+#define DQP_DYN_MODEL_LIST(X)                 \
+    X(DQP_DYN_PENDULUM1L, Robot<Pendulum1l>, 3)     \
+    X(DQP_DYN_CARTPOLE1L, Robot<Cartpole1l>, 5)     \
+    X(DQP_DYN_CARTPOLE2L, Robot<Cartpole2l>, 4)     \
+    X(DQP_DYN_PENDULUM_EULER, PendulumEuler, 3)     \
+    X(DQP_DYN_PENDULUM_DX, PendulumDx, 4)           \
+    X(DQP_DYN_REXQUADROTOR, RexQuadrotor, 2)        \
+    X(DQP_DYN_INTEGRATOR, Integrator, 3)
+
+template <class M, int KC_> struct ModelTag { using Map = M; static constexpr int KC = KC_; };
+
+// f(ModelTag of the model `id`), or `unknown` for an id that is not in the list.  f is a generic lambda:
+//   visit<int>(id, DQP_ERR_BAD_ARG, [&](auto model) { return run<typename decltype(model)::Map>(...); })
+template <class R, class F> __host__ __device__ __forceinline__ R visit(int id, R unknown, F &&f)
+{
+    switch (id) {
+#define X(ID, MAP, KC_) case ID: return f(ModelTag<MAP, KC_>{});
+    DQP_DYN_MODEL_LIST(X)
+#undef X
+    default: return unknown;
+    }
+}
+
+// is `id` registered, with these sizes?
+inline bool model_matches(int id, int n_state, int n_ctrl)
+{
+    return visit<bool>(id, false, [&](auto model) {
+        using Map = typename decltype(model)::Map;
+        return Map::NX == n_state && Map::NU == n_ctrl;
+    });
+}
 
 }  // namespace dyn
 }  // namespace dqp

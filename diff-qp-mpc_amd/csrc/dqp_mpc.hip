@@ -518,12 +518,7 @@ dqp_mpc_line_search(const dqp_mpc_dims *d, int dyn_id, double dt, const double *
     if (!x0 || !u || !x_new || !u_new || !alpha || !cost_new || max_iter < 1) return DQP_ERR_BAD_ARG;
     if (C && (!x || !delta_u || !c)) return DQP_ERR_BAD_ARG;
     if (!C) max_iter = 1;
-    if (dyn_id == 0) {
-        if (!F || !f) return DQP_ERR_BAD_ARG;
-    } else {
-        int32_t n = 0, m = 0;
-        if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
-    }
+    if (dyn_id == 0 ? (!F || !f) : !dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     LsP P = {};
     P.F = F; P.f = f; P.x0 = x0; P.x = x; P.u = u; P.du = delta_u; P.C = C; P.c = c;
     P.xn = x_new; P.un = u_new; P.alpha = alpha; P.cost = cost_new;
@@ -531,21 +526,17 @@ dqp_mpc_line_search(const dqp_mpc_dims *d, int dyn_id, double dt, const double *
     P.dyn = dyn_id; P.max_iter = max_iter;
     const dim3 grid((P.B + 63) / 64), block(64);
     hipStream_t st = (hipStream_t)stream;
-    using namespace dqp::dyn;
     switch (dyn_id) {
     case 0:
 #define X(a, b) if (P.n == a && P.m == b) { DQP_LAUNCH((line_search_kernel<LinStepT<a, b>>), grid, block, 0, st, P); break; }
         DQP_LIN_SIZES
 #undef X
         DQP_LAUNCH(line_search_kernel<LinStep>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM1L: DQP_LAUNCH(line_search_kernel<ModelStep<Robot<Pendulum1l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(line_search_kernel<ModelStep<Robot<Cartpole1l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE2L: DQP_LAUNCH(line_search_kernel<ModelStep<Robot<Cartpole2l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(line_search_kernel<ModelStep<PendulumEuler>>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(line_search_kernel<ModelStep<PendulumDx>>, grid, block, 0, st, P); break;
-    case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(line_search_kernel<ModelStep<RexQuadrotor>>, grid, block, 0, st, P); break;
-    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(line_search_kernel<ModelStep<Integrator>>, grid, block, 0, st, P); break;
-    default: return DQP_ERR_BAD_ARG;
+    default:        // a registered model: model_matches above
+        dqp::dyn::visit<int>(dyn_id, 0, [&](auto model) {
+            DQP_LAUNCH(line_search_kernel<ModelStep<typename decltype(model)::Map>>, grid, block, 0, st, P);
+            return 0;
+        });
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
@@ -560,32 +551,23 @@ dqp_mpc_rollout_backward(const dqp_mpc_dims *d, int dyn_id, double dt, const dou
     if (d->nbatch == 0) return DQP_OK;
     if (d->n_state > LS_MAXN || d->n_ctrl > LS_MAXM) return DQP_ERR_TOO_LARGE;
     if (!x || !u || !g_x) return DQP_ERR_BAD_ARG;
-    if (dyn_id == 0) {
-        if (!F) return DQP_ERR_BAD_ARG;
-    } else {
-        int32_t n = 0, m = 0;
-        if (dqp_dyn_sizes(dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
-    }
+    if (dyn_id == 0 ? (!F) : !dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     RbP P = {};
     P.F = F; P.x = x; P.u = u; P.g = g_x; P.dx0 = d_x0; P.du = d_u; P.dF = d_F; P.df = d_f;
     P.dt = dt; P.B = d->nbatch; P.n = d->n_state; P.m = d->n_ctrl; P.T = d->T; P.dyn = dyn_id;
     const dim3 grid((P.B + 63) / 64), block(64);
     hipStream_t st = (hipStream_t)stream;
-    using namespace dqp::dyn;
     switch (dyn_id) {
     case 0:
 #define X(a, b) if (P.n == a && P.m == b) { DQP_LAUNCH((rollout_backward_kernel<LinStepT<a, b>>), grid, block, 0, st, P); break; }
         DQP_LIN_SIZES
 #undef X
         DQP_LAUNCH(rollout_backward_kernel<LinStep>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM1L: DQP_LAUNCH(rollout_backward_kernel<ModelStep<Robot<Pendulum1l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE1L: DQP_LAUNCH(rollout_backward_kernel<ModelStep<Robot<Cartpole1l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_CARTPOLE2L: DQP_LAUNCH(rollout_backward_kernel<ModelStep<Robot<Cartpole2l>>>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_EULER: DQP_LAUNCH(rollout_backward_kernel<ModelStep<PendulumEuler>>, grid, block, 0, st, P); break;
-    case DQP_DYN_PENDULUM_DX: DQP_LAUNCH(rollout_backward_kernel<ModelStep<PendulumDx>>, grid, block, 0, st, P); break;
-    case DQP_DYN_REXQUADROTOR: DQP_LAUNCH(rollout_backward_kernel<ModelStep<RexQuadrotor>>, grid, block, 0, st, P); break;
-    case DQP_DYN_INTEGRATOR: DQP_LAUNCH(rollout_backward_kernel<ModelStep<Integrator>>, grid, block, 0, st, P); break;
-    default: return DQP_ERR_BAD_ARG;
+    default:        // a registered model: model_matches above
+        dqp::dyn::visit<int>(dyn_id, 0, [&](auto model) {
+            DQP_LAUNCH(rollout_backward_kernel<ModelStep<typename decltype(model)::Map>>, grid, block, 0, st, P);
+            return 0;
+        });
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }

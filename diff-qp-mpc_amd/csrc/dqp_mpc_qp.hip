@@ -8,6 +8,7 @@
 // could run it; the padded copies live in the caller's workspace behind the kernels' part (dqp_ric_pad.hip).
 #include "dqp_common.h"
 #include "dqp_al_bounds.h"
+#include "dqp_dyn_models.h"
 
 using namespace dqp;
 
@@ -63,10 +64,8 @@ int mpc_params(const dqp_mpc_dims *md, const dqp_opts *opts, KParams &P, size_t 
     rt = Route{};
     if (!dims_ok(md)) return DQP_ERR_BAD_ARG;
     if (md->n_state_host) return stage_params(md, opts, P, rt);
-    if (md->dyn_id) {       // true-dynamics residual: a registered model of this size
-        int32_t dn = 0, dm = 0;
-        if (dqp_dyn_sizes(md->dyn_id, &dn, &dm) != DQP_OK || dn != md->n_state || dm != md->n_ctrl) return DQP_ERR_BAD_ARG;
-    }
+    // true-dynamics residual: a registered model of this size
+    if (md->dyn_id && !dqp::dyn::model_matches(md->dyn_id, md->n_state, md->n_ctrl)) return DQP_ERR_BAD_ARG;
     dqp_dims d = {};
     d.nbatch = md->nbatch;
     d.nz = md->T * (md->n_state + md->n_ctrl);

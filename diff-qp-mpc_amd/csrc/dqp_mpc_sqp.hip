@@ -191,30 +191,21 @@ int run_linearize(long long N, const double *x, const double *u, double dt, doub
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
-// one instantiation per model, KC as in dqp_dyn_jacobian
+// one instantiation per model, at the model's KC
 int linearize(int dyn_id, long long N, double dt, const double *x, const double *u, double *F, double *f,
               const int32_t *state, hipStream_t st)
 {
-    using namespace dqp::dyn;
-    switch (dyn_id) {
-    case DQP_DYN_PENDULUM1L: return run_linearize<Robot<Pendulum1l>, 3>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_CARTPOLE1L: return run_linearize<Robot<Cartpole1l>, 5>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_CARTPOLE2L: return run_linearize<Robot<Cartpole2l>, 4>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_PENDULUM_EULER: return run_linearize<PendulumEuler, 3>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_PENDULUM_DX: return run_linearize<PendulumDx, 4>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_REXQUADROTOR: return run_linearize<RexQuadrotor, 2>(N, x, u, dt, F, f, state, st);
-    case DQP_DYN_INTEGRATOR: return run_linearize<Integrator, 3>(N, x, u, dt, F, f, state, st);
-    default: return DQP_ERR_BAD_ARG;
-    }
+    return dqp::dyn::visit<int>(dyn_id, DQP_ERR_BAD_ARG, [&](auto model) {
+        using M = decltype(model);
+        return run_linearize<typename M::Map, M::KC>(N, x, u, dt, F, f, state, st);
+    });
 }
 
 // DQP_OK: dims name a registered model of their own sizes
 int model_dims(const dqp_mpc_dims *d)
 {
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    int32_t n = 0, m = 0;
-    if (dqp_dyn_sizes(d->dyn_id, &n, &m) != DQP_OK || n != d->n_state || m != d->n_ctrl) return DQP_ERR_BAD_ARG;
-    return DQP_OK;
+    return dqp::dyn::model_matches(d->dyn_id, d->n_state, d->n_ctrl) ? DQP_OK : DQP_ERR_BAD_ARG;
 }
 
 // the caller's workspace, in doubles (include/dqp.h: dqp_mpc_sqp_workspace_bytes)

@@ -434,6 +434,9 @@ __device__ __forceinline__ void kkt_xy(const KParams &P, const Lds &S, double rx
 
 // ry = dyn_res(z) with the registered device model (qp_wrapper.py:326-345): z element i on lane i.
 // scratch: N + E doubles of LDS.  Rows: (T-1) n dynamics rows knot-major, then n rows x_0 - x0.
+// true_dyn_res has a case for every model whose n_state + n_ctrl is at most this.  The bound separates today's models
+// (knots of 3 to 7, the quadrotor's 16); it is no measured register or LDS limit: check both when a new model gets in.
+constexpr int DYN_RES_MAX_KNOT = 8;
 template <class Map>
 __device__ __forceinline__ void knot_step(const double *zs, int t, int nt, double dt, double *fs)
 {
@@ -455,15 +458,12 @@ __device__ __forceinline__ double true_dyn_res(const KParams &P, double *scratch
     if (lane < N) zs[lane] = z;
     WSYNC();
     if (lane < T - 1) {
-        switch (P.dynId) {
-        case DQP_DYN_PENDULUM1L: knot_step<dyn::Robot<dyn::Pendulum1l>>(zs, lane, nt, P.dynDt, fs); break;
-        case DQP_DYN_CARTPOLE1L: knot_step<dyn::Robot<dyn::Cartpole1l>>(zs, lane, nt, P.dynDt, fs); break;
-        case DQP_DYN_CARTPOLE2L: knot_step<dyn::Robot<dyn::Cartpole2l>>(zs, lane, nt, P.dynDt, fs); break;
-        case DQP_DYN_PENDULUM_EULER: knot_step<dyn::PendulumEuler>(zs, lane, nt, P.dynDt, fs); break;
-        case DQP_DYN_PENDULUM_DX: knot_step<dyn::PendulumDx>(zs, lane, nt, P.dynDt, fs); break;
-        case DQP_DYN_INTEGRATOR: knot_step<dyn::Integrator>(zs, lane, nt, P.dynDt, fs); break;
-        default: __builtin_trap();      // fill_params only lets the models above through
-        }
+        const bool fits = dyn::visit<bool>(P.dynId, false, [&](auto model) {
+            using Map = typename decltype(model)::Map;
+            if constexpr (Map::NX + Map::NU <= DYN_RES_MAX_KNOT) knot_step<Map>(zs, lane, nt, P.dynDt, fs);
+            return Map::NX + Map::NU <= DYN_RES_MAX_KNOT;
+        });
+        if (!fits) __builtin_trap();        // fill_params only lets the models whose knot fits through
     }
     WSYNC();
     double ry = 0.0;
@@ -743,10 +743,7 @@ int fill_params(const dqp_dims *d, const dqp_opts *o, KParams &P, size_t &lds_by
     if (P.dynId) {
         int32_t n = 0, m = 0;
         if (dqp_dyn_sizes(P.dynId, &n, &m) != DQP_OK) return DQP_ERR_BAD_ARG;
-        // models true_dyn_res evaluates on these one-QP-per-wavefront kernels (the quadrotor runs on the stage-wise ones)
-        if (P.dynId != DQP_DYN_PENDULUM1L && P.dynId != DQP_DYN_CARTPOLE1L && P.dynId != DQP_DYN_CARTPOLE2L &&
-            P.dynId != DQP_DYN_PENDULUM_EULER && P.dynId != DQP_DYN_PENDULUM_DX && P.dynId != DQP_DYN_INTEGRATOR)
-            return DQP_ERR_BAD_ARG;
+        if (n + m > DYN_RES_MAX_KNOT) return DQP_ERR_BAD_ARG;      // (the quadrotor runs on the stage-wise kernels)
         P.dynT = o->dyn_T; P.dynN = n; P.dynM = m; P.dynDt = o->dyn_dt; P.dynX0 = o->dyn_x0;
         if (P.dynT < 2 || P.dynT > WAVE || P.N != P.dynT * (n + m) ||
             (P.E != P.dynT * n && P.E != (P.dynT + 1) * n) || !P.dynX0)

@@ -501,26 +501,19 @@ __device__ __forceinline__ void model_residuals_of(const Ctx<C> &K)
 template <class C>
 __device__ __forceinline__ void model_residuals(const Ctx<C> &K0)
 {
-    using namespace dqp::dyn;
     const Ctx<C> K = fresh<C>(K0);
-    switch (K.P.dynId) {
-    case DQP_DYN_PENDULUM1L: model_residuals_of<C, Robot<Pendulum1l>>(K); break;
-    case DQP_DYN_CARTPOLE1L: model_residuals_of<C, Robot<Cartpole1l>>(K); break;
-    case DQP_DYN_CARTPOLE2L: model_residuals_of<C, Robot<Cartpole2l>>(K); break;
-    case DQP_DYN_PENDULUM_EULER: model_residuals_of<C, PendulumEuler>(K); break;
-    case DQP_DYN_PENDULUM_DX: model_residuals_of<C, PendulumDx>(K); break;
-    case DQP_DYN_REXQUADROTOR: model_residuals_of<C, RexQuadrotor>(K); break;
-    case DQP_DYN_INTEGRATOR: model_residuals_of<C, Integrator>(K); break;
-    default: break;
-    }
+    dqp::dyn::visit<int>(K.P.dynId, 0, [&](auto model) {
+        model_residuals_of<C, typename decltype(model)::Map>(K);
+        return 0;
+    });
 }
 
 template <class C> constexpr bool has_model()
 {
     using namespace dqp::dyn;
-    return model_fits<C, Robot<Pendulum1l>>() || model_fits<C, Robot<Cartpole1l>>() || model_fits<C, Robot<Cartpole2l>>() ||
-           model_fits<C, PendulumEuler>() || model_fits<C, PendulumDx>() || model_fits<C, RexQuadrotor>() ||
-           model_fits<C, Integrator>();
+#define X(ID, MAP, KC) model_fits<C, MAP>() ||
+    return DQP_DYN_MODEL_LIST(X) false;
+#undef X
 }
 
 // ---------------------------------------------------------------------------------------------
