@@ -469,40 +469,133 @@ __device__ __forceinline__ void tri_store(double *P, const double (&L)[S][N], in
     }
 }
 
-// y = L x with L the packed lower triangle in LDS (x, y distributed length N)
+// Build-time A/B switch of the LDS operand prefetch (default on; -DDQP_LDS_PREFETCH=0 gives the plain forms,
+// bit-identical in their results).  With one wavefront per SIMD nothing else runs while a wave sits in
+// s_waitcnt lgkmcnt for an operand it asked for just in time, so outside the iteration loop the LDS operands
+// of a dependent chain are fetched ahead of it: the triangular solves keep a ring of DQP_TRI_RING columns in
+// flight, the reflector chains the next reflector's tail, the row solves of the setup the next 8 entries.
+// The parts can be switched on their own (tools/ab_variants.py): DQP_PF_TRI, DQP_PF_REFLECT, DQP_PF_ROWS,
+// DQP_PF_HEADS.
+#ifndef DQP_LDS_PREFETCH
+#define DQP_LDS_PREFETCH 1
+#endif
+#ifndef DQP_TRI_RING
+#define DQP_TRI_RING 4         /* columns ahead: RING x one step's DPP chain (~18 cycles) > the LDS round trip */
+#endif
+#ifndef DQP_PF_TRI
+#define DQP_PF_TRI DQP_LDS_PREFETCH
+#endif
+
+// Orders a prefetch: every LDS read issued above stays above, whatever consumes x comes below (an LDS read
+// is ordered against the "memory" clobber, the arithmetic through x -- a scheduling barrier alone orders
+// only the reads, see dqp_r16n.hip).  No instruction.
+__device__ __forceinline__ void after_reads(double &x) { asm volatile("" : "+v"(x) : : "memory"); }
+
+// the lane's entries of column k of the packed triangle (rows >= k; slots wholly above k are not read)
 template <int S, int N>
+__device__ __forceinline__ void tri_col(const double *P, double (&c)[S], int k, int r)
+{
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if (16 * s + 15 < k) { c[s] = 0.0; continue; }
+        const int i = r + 16 * s;
+        const int ic = i < N ? i : N - 1;
+        c[s] = P[tri(ic) + (k <= ic ? k : 0)];
+    }
+}
+
+// Column k leaves the ring here: without this the selects that mask the entries (they depend on nothing else)
+// are scheduled right behind the read, and the wait with them.
+template <int S> __device__ __forceinline__ void ring_use(double (&c)[S], int k)
+{
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+        if (16 * s + 15 >= k) PIN(c[s]);
+}
+
+// y = L x with L the packed lower triangle in LDS (x, y distributed length N)
+template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
 __device__ __forceinline__ void tri_mv(const double *P, const double (&x)[S], double (&y)[S], int r)
 {
 #pragma unroll
     for (int s = 0; s < S; ++s) y[s] = 0.0;
+    if constexpr (D == 0) {                         // the plain form: each entry read where it is used
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double xb = BC(x, j);
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (16 * s + 15 < j) continue;
+                const int i = r + 16 * s;
+                const int ic = i < N ? i : N - 1;
+                const double v = P[tri(ic) + (j <= ic ? j : 0)];
+                y[s] = fma(mask_hi(v, j <= i && i < N), xb, y[s]);
+            }
+        }
+        return;
+    }
+    constexpr int DR = D > 0 ? D : 1;
+    double ring[DR][S];
+#pragma unroll
+    for (int j = 0; j < D && j < N; ++j) tri_col<S, N>(P, ring[j], j, r);
 #pragma unroll
     for (int j = 0; j < N; ++j) {
+        double col[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) col[s] = ring[j % DR][s];
+        if (j + D < N) tri_col<S, N>(P, ring[j % DR], j + D, r);
+        after_reads(y[S - 1]);
+        ring_use<S>(col, j);
         const double xb = BC(x, j);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (16 * s + 15 < j) continue;
             const int i = r + 16 * s;
-            const int ic = i < N ? i : N - 1;
-            const double v = P[tri(ic) + (j <= ic ? j : 0)];
-            y[s] = fma(mask_hi(v, j <= i && i < N), xb, y[s]);
+            y[s] = fma(mask_hi(col[s], j <= i && i < N), xb, y[s]);
         }
     }
 }
 
 // b <- L^-1 b with L packed in LDS (forward substitution; rd distributed reciprocal diagonal)
-template <int S, int N>
+template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
 __device__ __forceinline__ void tri_solve(const double *P, const double (&rd)[S], double (&b)[S], int r)
 {
+    if constexpr (D == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const int sk = k >> 4, lk = k & 15;
+            const double yk = rb(b[sk] * rd[sk], lk);
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (16 * s + 15 < k) continue;
+                const int i = r + 16 * s;
+                const int ic = i < N ? i : N - 1;
+                const double v = P[tri(ic) + (k <= ic ? k : 0)];
+                if (16 * s > k) b[s] = fma((i < N) ? -v : 0.0, yk, b[s]);
+                else b[s] = (r == lk) ? yk : fma((r > lk && i < N) ? -v : 0.0, yk, b[s]);
+            }
+        }
+        return;
+    }
+    constexpr int DR = D > 0 ? D : 1;
+    double ring[DR][S];
+#pragma unroll
+    for (int k = 0; k < D && k < N; ++k) tri_col<S, N>(P, ring[k], k, r);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const int sk = k >> 4, lk = k & 15;
+        double col[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) col[s] = ring[k % DR][s];
+        if (k + D < N) tri_col<S, N>(P, ring[k % DR], k + D, r);
+        after_reads(b[sk]);
+        ring_use<S>(col, k);
         const double yk = rb(b[sk] * rd[sk], lk);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (16 * s + 15 < k) continue;
             const int i = r + 16 * s;
-            const int ic = i < N ? i : N - 1;
-            const double v = P[tri(ic) + (k <= ic ? k : 0)];
+            const double v = col[s];
             if (16 * s > k) b[s] = fma((i < N) ? -v : 0.0, yk, b[s]);
             else b[s] = (r == lk) ? yk : fma((r > lk && i < N) ? -v : 0.0, yk, b[s]);
         }
@@ -511,20 +604,46 @@ __device__ __forceinline__ void tri_solve(const double *P, const double (&rd)[S]
 
 // b <- L^-T b with L packed in LDS: x_j = (b_j - sum_{i>j} L[i][j] x_i) / L[j][j]; the sum over
 // rows is a row reduction (the transposed access pattern of row-distributed storage).
-template <int S, int N>
+template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
 __device__ __forceinline__ void tri_solve_T(const double *P, const double (&rd)[S], double (&b)[S], int r)
 {
+    if constexpr (D == 0) {
+#pragma unroll
+        for (int j = N - 1; j >= 0; --j) {
+            const int sj = j >> 4, lj = j & 15;
+            double part = 0.0;
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (16 * s + 15 <= j) continue;
+                const int i = r + 16 * s;
+                const int ic = i < N ? i : N - 1;
+                const double v = P[tri(ic) + (j <= ic ? j : 0)];
+                part = fma((i > j && i < N) ? v : 0.0, b[s], part);
+            }
+            const double tot = row_sum(part);
+            if (r == lj) b[sj] = (b[sj] - tot) * rd[sj];
+        }
+        return;
+    }
+    constexpr int DR = D > 0 ? D : 1;
+    double ring[DR][S];
+#pragma unroll
+    for (int j = N - 1; j > N - 1 - D && j >= 0; --j) tri_col<S, N>(P, ring[j % DR], j, r);
 #pragma unroll
     for (int j = N - 1; j >= 0; --j) {
         const int sj = j >> 4, lj = j & 15;
+        double col[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) col[s] = ring[j % DR][s];
+        if (j - D >= 0) tri_col<S, N>(P, ring[j % DR], j - D, r);
+        after_reads(b[S - 1]);
+        ring_use<S>(col, j);
         double part = 0.0;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (16 * s + 15 <= j) continue;
             const int i = r + 16 * s;
-            const int ic = i < N ? i : N - 1;
-            const double v = P[tri(ic) + (j <= ic ? j : 0)];
-            part = fma((i > j && i < N) ? v : 0.0, b[s], part);
+            part = fma((i > j && i < N) ? col[s] : 0.0, b[s], part);
         }
         const double tot = row_sum(part);
         if (r == lj) b[sj] = (b[sj] - tot) * rd[sj];

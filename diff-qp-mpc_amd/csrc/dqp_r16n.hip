@@ -41,11 +41,28 @@ namespace r16n {
 
 using namespace dqp::r16;
 
+// the parts of DQP_LDS_PREFETCH (dqp_r16_prims.h) that live in this file
+#ifndef DQP_PF_REFLECT
+#define DQP_PF_REFLECT DQP_LDS_PREFETCH      /* apply_Qf / apply_QfT: the next reflector's tail */
+#endif
+#ifndef DQP_PF_ROWS
+#define DQP_PF_ROWS DQP_LDS_PREFETCH         /* row-uniform Lq / tail entries of the setup: 8 doubles ahead */
+#endif
+#ifndef DQP_PF_HEADS
+#define DQP_PF_HEADS DQP_LDS_PREFETCH        /* the epilogue's parked iterate: read ahead of the tails' barriers */
+#endif
+
 template <int N_, int M_, int E_> struct Cfg {
     static constexpr int N = N_, M = M_, E = E_, R = N_ - E_;
     static constexpr int SN = slots(N_), SM = slots(M_), SR = slots(N_ - E_);
     static constexpr int SE = E_ > 0 ? slots(E_) : 1, EC = E_ > 0 ? E_ : 1;
     static constexpr bool PARK = slots(N_) >= 3;        // W, U leave the registers between setup and epilogue
+    // The three-slot sizes keep the plain forms of DQP_LDS_PREFETCH: their forward kernels have no register to
+    // hold an operand ahead of its use -- each part alone adds scratch there (tools/kernel_resources.py:
+    // (35, 10, 30) 0 -> 44-80 B, (40, 20, 30) 336 -> 524-556 B).
+    static constexpr bool PF = !PARK;
+    static constexpr int RING = (PF && DQP_PF_TRI) ? DQP_TRI_RING : 0;
+    static constexpr bool PF_REFLECT = PF && DQP_PF_REFLECT, PF_ROWS = PF && DQP_PF_ROWS, PF_HEADS = PF && DQP_PF_HEADS;
 #ifndef DQP_R16N_PARK_WU
 #define DQP_R16N_PARK_WU 1
 #endif
@@ -155,7 +172,39 @@ __device__ __forceinline__ void shift_up(const double (&ve)[C::SE], double (&vn)
     }
 }
 
-// v <- H_k v for one reflector (u'_k read from LDS as a distributed vector)
+// the lane's entries of reflector k's tail u'_k (a distributed vector in LDS), as read
+template <class C>
+__device__ __forceinline__ void reflect_fetch(const double *lds, double (&t)[C::SN], int k, int r)
+{
+    const int ck = C::R + k;
+    const double *tl = lds + C::oTl + C::toff(k);
+#pragma unroll
+    for (int s = 0; s < C::SN; ++s) {
+        if (16 * s > ck) { t[s] = 0.0; continue; }
+        const int c = r + 16 * s;
+        t[s] = tl[c < ck ? c : 0];
+    }
+}
+// v <- H_k v for one reflector, t from reflect_fetch
+template <class C>
+__device__ __forceinline__ void reflect_apply(const double (&t)[C::SN], const double (&tau)[C::SE],
+                                              double (&v)[C::SN], int k, int r)
+{
+    const int ck = C::R + k;
+    double ud[C::SN], dot = 0.0;
+#pragma unroll
+    for (int s = 0; s < C::SN; ++s) {
+        if (16 * s > ck) { ud[s] = 0.0; continue; }
+        const int c = r + 16 * s;
+        ud[s] = c < ck ? t[s] : (c == ck ? 1.0 : 0.0);
+        dot = fma(ud[s], v[s], dot);
+    }
+    const double tw = BC(tau, k) * row_sum(dot);
+#pragma unroll
+    for (int s = 0; s < C::SN; ++s)
+        if (16 * s <= ck) v[s] = fma(-tw, ud[s], v[s]);
+}
+// v <- H_k v for one reflector (u'_k read from LDS as a distributed vector): the plain form
 template <class C>
 __device__ __forceinline__ void reflect1(const double *lds, const double (&tau)[C::SE],
                                          double (&v)[C::SN], int k, int r)
@@ -176,22 +225,73 @@ __device__ __forceinline__ void reflect1(const double *lds, const double (&tau)[
     for (int s = 0; s < C::SN; ++s)
         if (16 * s <= ck) v[s] = fma(-tw, ud[s], v[s]);
 }
+// v <- H_k0 ... v, then k0 + dk, ... : E reflectors.  With PF the tail of the next reflector is read before
+// this one's dot product -> row_sum -> update chain starts, so its LDS round trip runs under the chain.
+template <class C, bool PF>
+__device__ __forceinline__ void reflect_chain(const double *lds, const double (&tau)[C::SE],
+                                              double (&v)[C::SN], int k0, int dk, int r)
+{
+    if constexpr (!PF) {
+#pragma unroll
+        for (int n = 0; n < C::E; ++n) reflect1<C>(lds, tau, v, k0 + n * dk, r);
+        return;
+    }
+    double t[2][C::SN];
+    if (C::E > 0) reflect_fetch<C>(lds, t[0], k0, r);
+#pragma unroll
+    for (int n = 0; n < C::E; ++n) {
+        const int k = k0 + n * dk;
+        if (n + 1 < C::E) reflect_fetch<C>(lds, t[(n + 1) & 1], k + dk, r);
+        after_reads(v[0]);
+#pragma unroll
+        for (int s = 0; s < C::SN; ++s)          // (the tail is taken up here, not where it arrives)
+            if (16 * s <= C::R + k) PIN(t[n & 1][s]);
+        reflect_apply<C>(t[n & 1], tau, v, k, r);
+    }
+}
 // v <- Qf^T v = H_0 ... H_{E-1} v   (H_{E-1} first)
 template <class C>
 __device__ __forceinline__ void apply_QfT(const double *lds, const double (&tau)[C::SE],
                                           double (&v)[C::SN], int r)
 {
-#pragma unroll
-    for (int k = C::E - 1; k >= 0; --k) reflect1<C>(lds, tau, v, k, r);
+    reflect_chain<C, C::PF_REFLECT>(lds, tau, v, C::E - 1, -1, r);
 }
 // v <- Qf v = H_{E-1} ... H_0 v   (H_0 first)
 template <class C>
 __device__ __forceinline__ void apply_Qf(const double *lds, const double (&tau)[C::SE],
                                          double (&v)[C::SN], int r)
 {
-#pragma unroll
-    for (int k = 0; k < C::E; ++k) reflect1<C>(lds, tau, v, k, r);
+    reflect_chain<C, C::PF_REFLECT>(lds, tau, v, 0, 1, r);
 }
+
+// Row-uniform reads of the per-QP LDS array as a stream of 8-double chunks on the array's own 64-byte grid,
+// one chunk ahead of its use: element f is taken from registers, and the first element of a chunk issues the
+// reads of the chunk after it.  f only grows, by less than a chunk at a time; nothing past `last` is fetched
+// ahead.  Every index is a compile-time constant after unrolling.
+struct LdsStream {
+    double b[2][8];
+    int q;                       // b[q & 1] holds chunk q, chunk q + 1 is in flight into the other half
+};
+__device__ __forceinline__ void stream_chunk(const double *lds, LdsStream &t, int q)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t.b[q & 1][i] = lds[8 * q + i];
+}
+__device__ __forceinline__ void stream_open(const double *lds, LdsStream &t, int first, int last)
+{
+    t.q = first >> 3;
+    stream_chunk(lds, t, t.q);
+    if (t.q + 1 <= (last >> 3)) stream_chunk(lds, t, t.q + 1);
+}
+// true when f opened a new chunk (the caller then ties the reads just issued above its arithmetic)
+__device__ __forceinline__ bool stream_advance(const double *lds, LdsStream &t, int f, int last)
+{
+    if ((f >> 3) == t.q) return false;
+    t.q = f >> 3;
+    if (t.q + 1 <= (last >> 3)) stream_chunk(lds, t, t.q + 1);
+    return true;
+}
+__device__ __forceinline__ double stream_at(const LdsStream &t, int f) { return t.b[(f >> 3) & 1][f & 7]; }
 
 // t <- U^-T t  (U upper triangular E x E in Ah[:, R:], rows distributed in E-space)
 template <class C>
@@ -535,12 +635,27 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
         }
     }
     {
+        static_assert(C::oLq == 0, "the Lq stream runs on the LDS array's own chunk grid");
         const double *Lp = lds + C::oLq;
+        constexpr int lastLq = tri(N - 1) + N - 2;          // Lq[N-1][N-2]: the last entry phase B reads
+        LdsStream lq;
+        if (C::PF_ROWS && N > 1) stream_open(Lp, lq, tri(1), lastLq);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
 #pragma unroll
             for (int k = 0; k < j; ++k) {
-                const double ljk = Lp[tri(j) + k];
+                double ljk;
+                if (C::PF_ROWS) {
+                    // the next chunk's reads go out ahead of this chunk's FMAs -- for the last entries of a
+                    // column that is the first chunk of column j + 1, above this column's closing barrier
+                    if (stream_advance(Lp, lq, tri(j) + k, lastLq)) {
+                        if (E > 0) after_reads(st.Ah[0][j]);
+                        else if (!C::SPLIT) after_reads(st.Gh[0][j]);
+                    }
+                    ljk = stream_at(lq, tri(j) + k);
+                } else {
+                    ljk = Lp[tri(j) + k];
+                }
                 if (!C::SPLIT) {
 #pragma unroll
                     for (int s = 0; s < SM; ++s) st.Gh[s][j] = fma(-st.Gh[s][k], ljk, st.Gh[s][j]);
@@ -747,7 +862,7 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
         double ph[SN];
 #pragma unroll
         for (int s = 0; s < SN; ++s) ph[s] = p0[s];
-        tri_solve<SN, N>(C::SPLIT ? relabel(lds + C::oLq) : lds + C::oLq, st.rdq, ph, r);
+        tri_solve<SN, N, C::RING>(C::SPLIT ? relabel(lds + C::oLq) : lds + C::oLq, st.rdq, ph, r);
         if (E > 0) {
             apply_QfT<C>(lds, st.tau, ph, r);
             shift_down<C>(ph, st.py, r);
@@ -956,15 +1071,21 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
     // issued ahead of the barrier that frees the region (each lane reads what it stored itself in setup)
     CtxRegs<C::tailsz> tl;
     if (E > 0 && reload_tails) ctx_fetch<C::tailsz>(P.workspace + qp * (long long)C::wsQP + C::wTl, tl, r);
+    // recover x = Lq^-T Qf [w* ; xy],  y = U^-T (c* delta w1 - xy - py - W^T z*)
+    double bw[SR], bs[SM], bz[SM];
+    if (C::PF_HEADS) {     // the parked iterate is each lane's own (vec_put): read under the tails' round trip
+        vec_get<SR>(lds + C::oBw, bw, R, r);
+        vec_get<SM>(lds + C::oBs, bs, M, r);
+        vec_get<SM>(lds + C::oBz, bz, M, r);
+    }
     __syncthreads();
     if (E > 0 && reload_tails) ctx_stash<C::tailsz>(lds + C::oTl, tl, r);
     __syncthreads();
-
-    // recover x = Lq^-T Qf [w* ; xy],  y = U^-T (c* delta w1 - xy - py - W^T z*)
-    double bw[SR], bs[SM], bz[SM];
-    vec_get<SR>(lds + C::oBw, bw, R, r);
-    vec_get<SM>(lds + C::oBs, bs, M, r);
-    vec_get<SM>(lds + C::oBz, bz, M, r);
+    if (!C::PF_HEADS) {
+        vec_get<SR>(lds + C::oBw, bw, R, r);
+        vec_get<SM>(lds + C::oBs, bs, M, r);
+        vec_get<SM>(lds + C::oBz, bz, M, r);
+    }
     double xh[SN];
 #pragma unroll
     for (int s = 0; s < SN; ++s) xh[s] = (s < SR && r + 16 * s < R) ? bw[s < SR ? s : 0] : 0.0;
@@ -983,7 +1104,7 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
             yv[s] = (r + 16 * s < E) ? bestc * delta * st.w1[s] - st.xy[s] - st.py[s] - wz[s] : 0.0;
         solve_UT<C>(st, yv, r);
     }
-    tri_solve_T<SN, N>(lds + C::oLq, st.rdq, xh, r);
+    tri_solve_T<SN, N, C::RING>(lds + C::oLq, st.rdq, xh, r);
     if (live) {
 #pragma unroll
         for (int s = 0; s < SN; ++s)
@@ -1388,7 +1509,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P)
     for (int s = 0; s < SE; ++s) nu[s] = (E > 0 && inE[s]) ? P.nuin[qp * E + r + 16 * s] : 0.0;
 
     // gq = Qf^T Lq^-1 g
-    tri_solve<SN, N>(lds + C::oLq, st.rdq, g, r);
+    tri_solve<SN, N, C::RING>(lds + C::oLq, st.rdq, g, r);
     double gy[SE];
 #pragma unroll
     for (int s = 0; s < SE; ++s) gy[s] = 0.0;
@@ -1443,7 +1564,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P)
         for (int s = 0; s < SE; ++s) dnu[s] = inE[s] ? -(gy[s] + wz[s]) : 0.0;
         solve_UT<C>(st, dnu, r);
     }
-    tri_solve_T<SN, N>(lds + C::oLq, st.rdq, dxh, r);                   // dx = Lq^-T dxh
+    tri_solve_T<SN, N, C::RING>(lds + C::oLq, st.rdq, dxh, r);                   // dx = Lq^-T dxh
 
     if (!live) return;
     if (P.mdc || P.mdC || P.mdF || P.mdf || P.mdx0) {
