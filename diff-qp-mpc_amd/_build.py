@@ -47,7 +47,7 @@ RIC_PARTS = [("native", RIC_SIZES), ("wide", RICW_SIZES)] + [("host%d" % k, p) f
 
 PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_mpc_qp.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip",
                  "dqp_al_banded.hip", "dqp_al_banded_wide.hip", "dqp_trace.hip", "dqp_big.hip", "dqp_shared_grad.hip",
-                 "dqp_al_fused.hip", "dqp_mpc_sqp.hip"]
+                 "dqp_al_fused.hip", "dqp_mpc_sqp.hip", "dqp_deq.hip"]
 SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric.hip", "dqp_ric_pad.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-MD",
          "-mllvm", "-pragma-unroll-threshold=10000000", "-mllvm", "-unroll-threshold=10000000"]

@@ -70,6 +70,9 @@ class dqp_mpc_dims(ctypes.Structure):
                 ("n_state_host", ctypes.c_int32)]     # 0 unless given: positional constructions keep the native routes
 
 
+class dqp_deq_dims(ctypes.Structure):
+    _fields_ = [("nrows", ctypes.c_int32), ("hdim", ctypes.c_int32)]
+
 
 class dqp_trace_record(ctypes.Structure):
     _fields_ = [("kernel", ctypes.c_char * 248), ("ms", ctypes.c_float), ("reserved", ctypes.c_int32)]
@@ -77,7 +80,7 @@ class dqp_trace_record(ctypes.Structure):
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 _STRUCTS = {c.__name__: c for c in (dqp_dims, dqp_opts, dqp_mpc_dims, dqp_al_dims, dqp_al_mpc_dims, dqp_al_bounds,
-                                    dqp_trace_record)}
+                                    dqp_deq_dims, dqp_trace_record)}
 _STRUCTS["dqp_mpc_bounds"] = dqp_al_bounds        # a typedef in the header
 
 

@@ -2,7 +2,8 @@
 fused kernels.
 
     DEQLayer       policies.py:191-430   the MLP variant (layer_type "mlp"; state-dict keys as the
-                                         reference's, so its checkpoints load)
+                                         reference's, so its checkpoints load); with FUSED_DEQ_LAYER its LayerNorm /
+                                         ReLU / residual stages run on the fused fp32 kernels (deq_fused)
     Tracking_MPC   policies.py:567-686   p = -(Q x_ref); AL_mpc.MPC ("al", the reference's default,
                                          deqmpc/train.py:61) or qp_wrapper.MPC ("ip")
     DEQMPCPolicy   policies.py:432-529   deq_iter x [DEQLayer -> Tracking_MPC]; every iterate is returned
@@ -26,6 +27,7 @@ from . import AL_mpc as al_mpc
 from .dynamics import DeviceDynamics, recognise
 from . import al_utils
 from . import qp_wrapper as ip_mpc
+from . import deq_fused
 
 
 # Tracking_MPC: look at the env's dynamics module and use the registered device model when it is one (dynamics.recognise)
@@ -34,6 +36,11 @@ RECOGNISE_ENV_DYNAMICS = True
 
 # batch rows from which the DEQLayer's linears take their weight gradient in slices (SlicedLinear below)
 SLICED_WGRAD_FROM = 8192
+
+# DEQLayer: run the LayerNorm / ReLU / residual stages between its GEMMs on the fused fp32 kernels (deq_fused,
+# csrc/dqp_deq.hip).  A permission, as AL_mpc.PERSISTENT_SOLVE is: activations that are not CUDA fp32, a width the
+# kernels do not serve or a LayerNorm without affine take the torch code below.
+FUSED_DEQ_LAYER = False
 
 
 class SlicedLinear(torch.autograd.Function):
@@ -103,11 +110,19 @@ class DEQLayer(nn.Module):
         return torch.zeros(bsz, self.hdim, dtype=torch.float32, device=p.device)
 
     def deq_layer(self, x, z):                                                    # policies.py:277-283
+        if FUSED_DEQ_LAYER and deq_fused.usable((self.lndeq1, self.lndeq2, self.lndeq3), (x, z)):
+            z = deq_fused.layer_norm(_linear(self.fcdeq1, z), self.lndeq1, relu=True)
+            return deq_fused.residual_block(x, _linear(self.fcdeq2, z), z, self.lndeq2, self.lndeq3)
         z = self.lndeq1(self.reludeq1(_linear(self.fcdeq1, z)))
         return self.lndeq3(self.reludeq2(z + self.lndeq2(x + _linear(self.fcdeq2, z))))
 
+    def _inp_norm(self, h):
+        if FUSED_DEQ_LAYER and deq_fused.usable((self.inp_layer[1],), (h,)):
+            return deq_fused.layer_norm(h, self.inp_layer[1], relu=False)
+        return self.inp_layer[1](h)
+
     def forward(self, x, z):
-        z_out = self.deq_layer(self.inp_layer[1](_linear(self.inp_layer[0], x)), z)
+        z_out = self.deq_layer(self._inp_norm(_linear(self.inp_layer[0], x)), z)
         steps = self.T - 1 if self.out_type == 1 else self.T
         dx_ref = _linear(self.out_layer[0], z_out).view(-1, steps, self.nx)
         vel_ref = dx_ref[..., self.nq:]

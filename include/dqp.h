@@ -32,7 +32,9 @@ extern "C" {
                            shared parameters summed over the batch on the device; dqp_al_mpc_solve_fused_supported /
                            dqp_al_mpc_solve_fused_bytes / dqp_al_mpc_solve_fused -- dqp_al_mpc_solve as one launch;
                            dqp_mpc_linearize, dqp_mpc_sqp_supported / _workspace_bytes / _rounds -- the SQP rounds of
-                           qp_wrapper.MPC for a registered model, enqueued by one call;)
+                           qp_wrapper.MPC for a registered model, enqueued by one call;
+                           dqp_deq_supported / _partial_bytes / _ln_forward / _ln_backward / _res_forward / _res_backward --
+                           the LayerNorm stages of the DEQ-MPC network as fused fp32 kernels;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -851,6 +853,59 @@ typedef struct dqp_trace_record {
 } dqp_trace_record;
 int dqp_trace_begin(int32_t max_launches);      /* launches beyond max_launches are not recorded */
 int dqp_trace_end(dqp_trace_record *out, int32_t capacity, int32_t *count);  /* out: HOST memory */
+
+/* ------------------------------------------------------------------ network-side kernels (fp32)
+ * The one exception to "all pointers fp64": the trajectory network of DEQ-MPC runs in single precision
+ * (deqmpc/policies.py:191-430, DEQLayer), and so do these entries -- every `float *` below is a DEVICE pointer to
+ * fp32, row-major, contiguous and 16-byte aligned (a misaligned pointer is DQP_ERR_BAD_ARG).  Scalars stay double /
+ * int32_t.  They replace, between the three GEMMs of one DEQLayer iteration (policies.py:277-283), the LayerNorm, ReLU
+ * and residual-add kernels, forward and backward, with one pass per stage (csrc/dqp_deq.hip):
+ *
+ *   stage A   y  = LN(relu ? max(a, 0) : a; gamma, beta, eps)        relu 0: inp_layer[1]; relu 1: lndeq1(reludeq1(.))
+ *   stage B   z2 = LN(max(z1 + LN(xi + a2; gamma2, beta2, eps2), 0); gamma3, beta3, eps3)
+ *                                                                    lndeq3(reludeq2(z1 + lndeq2(xi + fcdeq2(z1))))
+ *
+ * with LN of torch.nn.LayerNorm over the last axis: biased variance, rstd = 1 / sqrt(var + eps), two-pass statistics.
+ * a, y, xi, a2, z1, z2 and their cotangents are (nrows, hdim); gamma*, beta* (hdim).  hdim is 32, 64, 128, 256 or 512
+ * (hdim / 64 elements per lane, a row per wavefront; two rows per wavefront at 32).
+ * stats: (nrows, 2) = mean, rstd of stage A; (nrows, 4) = mean2, rstd2, mean3, rstd3 of stage B -- written by the
+ * forward, read by the backward, which recomputes everything else from the stage's inputs (nothing of size
+ * (nrows, hdim) is kept).  The ReLU derivative is (input > 0).
+ * Backward outputs: stage A da; stage B ds (the cotangent of xi AND of a2, one tensor) and dz1 (through the residual
+ * only: a2's dependence on z1 is the caller's GEMM); dgamma*, dbeta* (hdim) are sums over the rows.  Any of them may be
+ * NULL to skip it.
+ * The row sums use no atomics: a workgroup owns a fixed set of consecutive rows, adds them in row order and leaves one
+ * partial per workgroup in `partial`; a second kernel adds the partials in ascending order (fp64 accumulator, rounded
+ * once).  The result depends only on
+ * the inputs, nrows and hdim: bit-identical from run to run.  partial: dqp_deq_partial_bytes(dims) bytes of device
+ * scratch =
+ *     16 * hdim * ceil(U / (4 * max(2, ceil(U / 4096)))),     U = nrows (hdim >= 64) or ceil(nrows / 2) (hdim 32)
+ * (at most 1024 partials of four hdim-vectors); needed when a dgamma / dbeta is asked for, else it may be NULL.
+ * dqp_deq_supported: 1 for nrows >= 0 and one of the five hdim, else (and for NULL) 0; _partial_bytes is 0 there.
+ * Both are host functions and need no device.
+ * Return codes, decided on the host in front of any launch, in this order: DQP_ERR_BAD_ARG for a null `dims` or
+ * nrows < 0; DQP_ERR_TOO_LARGE for another hdim; DQP_OK with nothing touched at nrows == 0; DQP_ERR_BAD_ARG for a null
+ * (or misaligned) array.  Calls only enqueue on `stream` (one launch forward; backward one, plus the finish kernel
+ * when a parameter gradient is asked for): no allocation, no synchronisation, hipGraph-capturable.
+ */
+typedef struct dqp_deq_dims {
+    int32_t nrows;
+    int32_t hdim;
+} dqp_deq_dims;
+
+int dqp_deq_supported(const dqp_deq_dims *dims);
+size_t dqp_deq_partial_bytes(const dqp_deq_dims *dims);
+int dqp_deq_ln_forward(const dqp_deq_dims *dims, const float *a, const float *gamma, const float *beta, double eps,
+                       int32_t relu, float *y, float *stats, void *stream);
+int dqp_deq_ln_backward(const dqp_deq_dims *dims, const float *a, const float *gamma, const float *stats, int32_t relu,
+                        const float *dy, float *da, float *dgamma, float *dbeta, float *partial, void *stream);
+int dqp_deq_res_forward(const dqp_deq_dims *dims, const float *xi, const float *a2, const float *z1,
+                        const float *gamma2, const float *beta2, const float *gamma3, const float *beta3, double eps2,
+                        double eps3, float *z2, float *stats, void *stream);
+int dqp_deq_res_backward(const dqp_deq_dims *dims, const float *xi, const float *a2, const float *z1,
+                         const float *gamma2, const float *beta2, const float *gamma3, const float *stats,
+                         const float *dz2, float *ds, float *dz1, float *dgamma2, float *dbeta2, float *dgamma3,
+                         float *dbeta3, float *partial, void *stream);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,8 @@ nx, nu = dyn.n_state, dyn.n_ctrl
 ub = 250.0 if robot == "cartpole2l" else 100.0
 env = types.SimpleNamespace(nx=nx, nu=nu, nq=nx // 2, dt=dyn.dt, dynamics=dyn, dynamics_derivatives=dyn.jac,
                             action_space=types.SimpleNamespace(high=np.array([ub] * nu), low=np.array([-ub] * nu)))
-args = argparse.Namespace(T=T, nq=nx // 2, hdim=256, layer_type="mlp", deq_out_type=1, policy_out_type=1, deq_iter=deq_iter,
+policies.FUSED_DEQ_LAYER = os.environ.get("FUSED_DEQ_LAYER") == "1"      # the DEQLayer's LayerNorm stages on csrc/dqp_deq.hip
+args = argparse.Namespace(T=T, nq=nx // 2, hdim=int(os.environ.get("HDIM", 256)), layer_type="mlp", deq_out_type=1, policy_out_type=1, deq_iter=deq_iter,
                           solver_type="al", qp_iter=1, eps=1e-2, warm_start=True, bsz=B,
                           Q=torch.ones(nx), R=1e-2 * torch.ones(nu), dtype="double", device="cuda")
 torch.manual_seed(0)
@@ -55,7 +56,7 @@ for _ in range(reps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / reps
 if rank == 0:
-    print("DEQ-MPC train step %s  B=%d/GPU x %d GPU(s)  T=%d deq_iter=%d: %.1f ms per step, %.0f k trajectories/s (whole job), loss %.4f"
-          % (robot, B, world, T, deq_iter, dt * 1e3, B * world / dt / 1e3, float(loss)))
+    print("DEQ-MPC train step %s  B=%d/GPU x %d GPU(s)  T=%d deq_iter=%d hdim=%d fused_deq_layer=%d: %.1f ms per step, %.0f k trajectories/s (whole job), loss %.4f"
+          % (robot, B, world, T, deq_iter, args.hdim, policies.FUSED_DEQ_LAYER, dt * 1e3, B * world / dt / 1e3, float(loss)))
 if world > 1:
     dist.destroy_process_group()
