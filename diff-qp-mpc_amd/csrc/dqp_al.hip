@@ -26,6 +26,7 @@
 #include "dqp_r16_prims.h"
 #include "dqp_dyn_models.h"   // row_sum (DPP row reduction)
 #include "dqp_al_bounds.h"
+#include "dqp_al_banded.h"
 
 #ifdef DQP_STAMPS
 namespace dqp { extern unsigned long long *g_debug_stamps; }
@@ -1105,6 +1106,21 @@ int launch(K kernel, const AlP &P, size_t lds, void *stream, int threads = 256)
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 
+// the dense Newton step: al_newton_kernel at the number of 16-column slots nz takes
+int launch_newton(const AlP &P, size_t lds, void *stream)
+{
+    switch ((P.nz + 15) / 16) {
+    case 1: return launch(al_newton_kernel<1>, P, lds, stream);
+    case 2: return launch(al_newton_kernel<2>, P, lds, stream);
+    case 3: return launch(al_newton_kernel<3>, P, lds, stream);
+    case 4: return launch(al_newton_kernel<4>, P, lds, stream);
+    case 5: return launch(al_newton_kernel<5>, P, lds, stream);
+    case 6: return launch(al_newton_kernel<6>, P, lds, stream);
+    case 7: return launch(al_newton_kernel<7>, P, lds, stream);
+    default: return launch(al_newton_kernel<8>, P, lds, stream);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1120,16 +1136,7 @@ dqp_al_newton_step(const dqp_al_dims *dims, const double *Jc, const double *Qdia
     if (P.B == 0) return DQP_OK;
     if ((!Jc && P.ncon > 0) || !Qdiag || !rho || !grad || !update) return DQP_ERR_BAD_ARG;
     P.Jc = Jc; P.Qd = Qdiag; P.rho = rho; P.grad = grad; P.update = update; P.L = L; P.info = info;
-    switch ((P.nz + 15) / 16) {
-    case 1: return launch(al_newton_kernel<1>, P, lds, stream);
-    case 2: return launch(al_newton_kernel<2>, P, lds, stream);
-    case 3: return launch(al_newton_kernel<3>, P, lds, stream);
-    case 4: return launch(al_newton_kernel<4>, P, lds, stream);
-    case 5: return launch(al_newton_kernel<5>, P, lds, stream);
-    case 6: return launch(al_newton_kernel<6>, P, lds, stream);
-    case 7: return launch(al_newton_kernel<7>, P, lds, stream);
-    default: return launch(al_newton_kernel<8>, P, lds, stream);
-    }
+    return launch_newton(P, lds, stream);
 }
 
 __attribute__((visibility("default"))) int
@@ -1305,16 +1312,7 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
         DQP_LAUNCH(al_assemble_kernel, dim3(B), dim3(256), 0, st, As);
         AlP P = A;
         P.Jc = Jc; P.Qd = Qdiag; P.rho = rho; P.grad = grad; P.update = upd; P.L = L; P.info = info;
-        switch ((nz + 15) / 16) {
-        case 1: rc = launch(al_newton_kernel<1>, P, lds, stream); break;
-        case 2: rc = launch(al_newton_kernel<2>, P, lds, stream); break;
-        case 3: rc = launch(al_newton_kernel<3>, P, lds, stream); break;
-        case 4: rc = launch(al_newton_kernel<4>, P, lds, stream); break;
-        case 5: rc = launch(al_newton_kernel<5>, P, lds, stream); break;
-        case 6: rc = launch(al_newton_kernel<6>, P, lds, stream); break;
-        case 7: rc = launch(al_newton_kernel<7>, P, lds, stream); break;
-        default: rc = launch(al_newton_kernel<8>, P, lds, stream); break;
-        }
+        rc = launch_newton(P, lds, stream);
         if (rc) return rc;
         LsAPS Lc = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id}, bsb, bst};
         rc = launch_ls(Lc, st);

@@ -1,5 +1,5 @@
-// dqp_al_banded_wide.hip -- the block-tridiagonal NewtonAL kernels of dqp_al_banded.hip for caller-linearised dynamics
-// with knots of 17 to 32 variables (16 < n + m <= 32): the same kernels, instantiated here on DQP_BAND_WIDE_SIZES.
+// dqp_al_banded_wide.hip -- the block-tridiagonal NewtonAL kernels (dqp_al_banded_kernels.h) for caller-linearised
+// dynamics with knots of 17 to 32 variables (16 < n + m <= 32): the same kernels, instantiated here on DQP_BAND_WIDE_SIZES.
 //
 // Layout: one problem per 32-lane half-wavefront (two problems per wavefront), a knot's nt rows one per lane
 // (r = lane & 31) exactly as in the 16-lane form, so the sweeps are the same source: the large-model forward sweep (state
@@ -9,41 +9,20 @@
 // keeps its form: per (b, t) nt rows x (nt + 1 + n) doubles, element-major over the knot's lanes
 // (dqp_al_banded_jac_factor_bytes).  No prefetch-ahead, half-row or LDS-factor variants, and no registered model is
 // this wide.
-#define DQP_AL_BANDED_KERNELS_ONLY
-#include "dqp_al_banded.hip"
+#include "dqp_al_banded_kernels.h"
 
-#include <type_traits>
-static_assert(std::is_trivially_copyable<BandP>::value && std::is_standard_layout<BandP>::value,
-              "BandP crosses translation units by address");
-
-namespace dqp {
-
-int al_banded_wide_newton(int n, int m, const void *bandp, size_t bandp_bytes, void *stream)
+int dqp::al_banded_wide_newton(int n, int m, const BandP &P, void *stream)
 {
-    if (!bandp || bandp_bytes != sizeof(BandP)) return DQP_ERR_BAD_ARG;
-    BandP P = *static_cast<const BandP *>(bandp);
-#define X(a, b)                                                                                                          \
-    if (n == a && m == b) {                                                                                              \
-        DQP_LAUNCH((al_banded_newton_kernel<Given<a, b>, 32>), dim3((P.B + 1) / 2), dim3(64), 0, (hipStream_t)stream, P); \
-        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;                                                \
-    }
-    DQP_BAND_WIDE_SIZES
-#undef X
-    return DQP_ERR_TOO_LARGE;
+    return visit_pair<BAND_WIDE, int>(n, m, DQP_ERR_TOO_LARGE, [&](auto given) {
+        DQP_LAUNCH((al_banded_newton_kernel<decltype(given), 32>), dim3((P.B + 1) / 2), dim3(64), 0, (hipStream_t)stream, P);
+        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    });
 }
 
-int al_banded_wide_solve(int n, int m, const void *bandp, size_t bandp_bytes, void *stream)
+int dqp::al_banded_wide_solve(int n, int m, const BandP &P, void *stream)
 {
-    if (!bandp || bandp_bytes != sizeof(BandP)) return DQP_ERR_BAD_ARG;
-    BandP P = *static_cast<const BandP *>(bandp);
-#define X(a, b)                                                                                                         \
-    if (n == a && m == b) {                                                                                             \
-        DQP_LAUNCH((al_banded_solve_kernel<Given<a, b>, 32>), dim3((P.B + 1) / 2), dim3(64), 0, (hipStream_t)stream, P); \
-        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;                                               \
-    }
-    DQP_BAND_WIDE_SIZES
-#undef X
-    return DQP_ERR_TOO_LARGE;
+    return visit_pair<BAND_WIDE, int>(n, m, DQP_ERR_TOO_LARGE, [&](auto given) {
+        DQP_LAUNCH((al_banded_solve_kernel<decltype(given), 32>), dim3((P.B + 1) / 2), dim3(64), 0, (hipStream_t)stream, P);
+        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    });
 }
-
-}  // namespace dqp

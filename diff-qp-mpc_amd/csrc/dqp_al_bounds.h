@@ -1,5 +1,5 @@
 // dqp_al_bounds.h -- the bound layout of the AL kernels (include/dqp.h: dqp_al_bounds), shared by dqp_al.hip,
-// dqp_al_banded.hip and dqp_al_fused.hip.
+// the banded kernels (dqp_al_banded_kernels.h) and dqp_al_fused.hip.
 //
 // A kernel template instantiated on StridedBounds<Map> reads the control bounds of sample b, knot t, control k at
 // [b stride_b + t stride_t + k]; instantiated on the plain Map it reads the n_ctrl-vector as it always did: the strided
@@ -40,12 +40,6 @@ inline int mpc_bounds_layout(const dqp_mpc_bounds *b, const dqp_mpc_dims *d)
     const bool ok = (sb == 0 && (st == 0 || st == m)) || (sb == m && (st == 0 || st == Bm)) || (sb == Tm && st == m);
     return ok ? DQP_OK : DQP_ERR_BAD_ARG;
 }
-
-// dqp_al_banded.hip: dqp_al_banded_newton_step_bounds with `keep` = does the caller use this step's factor afterwards
-int al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
-                                      const double *Qdiag, const double *q, const double *lam, const double *rho,
-                                      const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info, void *stream,
-                                      int keep);
 
 }  // namespace dqp
 #endif

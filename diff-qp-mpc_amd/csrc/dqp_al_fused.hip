@@ -29,10 +29,9 @@
 //
 // Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2, the integrator),
 // 2 <= T <= 32, fp64.  RexQuadrotor (12 + 4) stays on the multi-launch path.
-#define DQP_AL_BANDED_KERNELS_ONLY
-#include "dqp_al_banded.hip"
-
 #include <type_traits>
+
+#include "dqp_al_banded_kernels.h"
 
 namespace {
 

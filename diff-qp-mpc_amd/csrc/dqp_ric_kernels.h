@@ -51,7 +51,7 @@ using namespace dqp::r16;
 #endif
 
 // Cross-lane primitives over the G lanes of one problem: bc<G> / gsum<G> / gmin<G> of dqp_r16_prims.h (shared with the
-// wide block-tridiagonal NewtonAL kernels, dqp_al_banded.hip).
+// wide block-tridiagonal NewtonAL kernels, dqp_al_banded_kernels.h).
 
 // the 16-lane host-only pairs: _build.py hands every object that includes this file the same list
 #ifndef DQP_RIC_HOST16_SIZES

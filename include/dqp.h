@@ -580,7 +580,7 @@ int dqp_al_banded_solve(const dqp_al_mpc_dims *dims, int dyn_id, const void *fac
  * model.  Lifts the nz <= 128 limit of dqp_al_newton_step for user dynamics (config 4 with the reference's
  * own quadrotor module: nz = 480).  Compiled (n_state, n_ctrl) pairs: DQP_BAND_SIZES (n_state + n_ctrl <= 16: one
  * problem per 8 or 16 lanes) and DQP_BAND_WIDE_SIZES (16 < n_state + n_ctrl <= 32: one problem per 32-lane
- * half-wavefront, csrc/dqp_al_banded_wide.hip) in csrc/dqp_al_banded.hip; others return DQP_ERR_TOO_LARGE.
+ * half-wavefront, csrc/dqp_al_banded_wide.hip) in csrc/dqp_al_banded_kernels.h; others return DQP_ERR_TOO_LARGE.
  * `factor` has dqp_al_banded_jac_factor_bytes(dims) bytes and is applied by dqp_al_banded_solve(dims, 0, ...).
  *
  * dqp_al_banded_jac_factor_bytes: the factor buffer size of this call at every pair it accepts -- at the

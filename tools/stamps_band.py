@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-phase s_memtime split of the block-tridiagonal Newton kernel's forward sweep (large models: the quadrotor) --
-instrumented build of csrc/dqp_al_banded.hip (-DDQP_BAND_STAMPS), config-4 shape.
+instrumented build (-DDQP_BAND_STAMPS) of csrc/dqp_al_banded.hip, the object that instantiates the kernels of
+csrc/dqp_al_banded_kernels.h for knots of up to 16 variables; config-4 shape.  The flag adds a second argument to that
+object's Newton kernel and leaves the shared argument block alone, so the other objects link as they are.
     python tools/ab_variants.py build dqp_al_banded.hip stamps=diff-qp-mpc_amd/csrc/dqp_al_banded.hip,-DDQP_BAND_STAMPS   (CPU box)
     DQP_HIP_LIBRARY=diff-qp-mpc_amd/csrc/libdqp_hip_ab_stamps.so python tools/stamps_band.py                               (GPU box)
 Every stamp drains the memory counters: phases do not overlap as in the shipped kernel."""
