@@ -9,6 +9,14 @@
 State carried across calls, as in the reference (AL_mpc.py:193-195,250-251,314-318): `lamda_prev`,
 `rho_prev`, `cost_lam_hist` (the warm start looks up the stored AL iterate whose cost was already
 below the new starting cost), `x_init`, `u_init`, `just_initialized`.
+
+State bounds (`x_lower` / `x_upper`, both or neither; finite; (n,), (T, n), (B, 1, n) or (B, T, n)): rows
+[x_t - x_upper, x_lower - x_t] of every knot, appended behind the control rows -- the multipliers then have
+T n + 2 T m + 2 T n columns.  A registered device model (n_state + n_ctrl <= 16, n_state <= 12, fp64) runs them on the
+block-tridiagonal kernels (dqp_al_mpc_solve_xbounds, or per AL iteration dqp_al_newton_solve_xbounds +
+dqp_al_outer_update_xbounds; the backward is the one without them).  Everything else takes the general torch path with
+the state rows: the single-launch solve (PERSISTENT_SOLVE), caller-linearised dynamics (NewtonALBandedJac), the dense
+AL kernel route, and the LU fallback after a Cholesky failure.
 """
 import torch
 from torch.nn import Module
@@ -73,7 +81,7 @@ class MPC(Module):
                  max_linesearch_iter=10, exit_unconverged=True, detach_unconverged=True,
                  backprop=True, slew_rate_penalty=None, solver_type='dense',
                  add_goal_constraint=False, x_goal=None, diag_cost=True, ineqG=None, ineqh=None,
-                 dtype=torch.float64):
+                 dtype=torch.float64, x_lower=None, x_upper=None):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -87,6 +95,15 @@ class MPC(Module):
         self.u_lower = _detach(u_lower.to(dtype))
         self.u_upper = _detach(u_upper.to(dtype))
         self.x_lower = self.x_upper = None
+        if (x_lower is None) != (x_upper is None):
+            raise ValueError("state bounds: give both x_lower and x_upper, or neither")
+        if x_lower is not None:
+            al_utils._bound_strides(x_lower, x_upper, n_batch, T, n_state)       # ValueError for a shape without a layout
+            if not (bool(torch.isfinite(x_lower).all()) and bool(torch.isfinite(x_upper).all())):
+                raise ValueError("state bounds must be finite (an infinite bound makes 0 * inf in lam . res): use a large "
+                                 "finite number, e.g. 1e30, where a state is free")
+            self.x_lower = _detach(x_lower.to(dtype)).contiguous()
+            self.x_upper = _detach(x_upper.to(dtype)).contiguous()
         self.x_goal, self.ineqG, self.ineqh = x_goal, ineqG, ineqh
         self.u_init, self.x_init = _detach(u_init), _detach(x_init)
         self.verbose, self.eps, self.back_eps, self.n_batch = verbose, eps, back_eps, n_batch
@@ -95,7 +112,7 @@ class MPC(Module):
         self.backprop, self.slew_rate_penalty, self.solver_type = backprop, slew_rate_penalty, solver_type
         self.add_goal_constraint, self.diag_cost, self.al_iter = add_goal_constraint, diag_cost, al_iter
         self.neq = n_state * T
-        self.nineq = 2 * n_ctrl * T
+        self.nineq = 2 * n_ctrl * T + (2 * n_state * T if self.x_lower is not None else 0)
         self.dyn_res_crit, self.dyn_res_factor = 1e-4, 10
         self.rho_prev = 1.0
         self.lamda_prev = torch.zeros(n_batch, self.neq + self.nineq, dtype=self.u_upper.dtype, device=self.u_upper.device)
@@ -139,8 +156,11 @@ class MPC(Module):
         nt = self.n_state + self.n_ctrl
         banded = al_utils.BANDED_NEWTON_AL and nt <= 16                # one knot per 16-lane DPP row
         dense = self.n_state <= 8 and self.n_ctrl <= 2 and self.T * nt <= 128
+        xb = self.x_lower is not None
+        # state bounds: the block-tridiagonal kernels only (fp64, n_state <= 12); everything else the general path
+        xb_ok = not xb or (banded and self.n_state <= 12 and dt == torch.float64 and x.is_cuda)
         device_path = (_fused and FUSED_NEWTON_AL and isinstance(dx, DeviceDynamics) and (banded or dense)
-                       and self.x_lower is None
+                       and xb_ok
                        and al_utils.bounds_supported(self.u_lower, self.u_upper, x.size(0), self.T, self.n_ctrl))
         strided = al_utils.bounds_strided(self.u_lower, self.n_ctrl)      # per-sample / per-knot bounds
         if (ONE_CALL_SOLVE and device_path and banded and al_utils.BANDED_NEWTON_AL and torch.is_tensor(self.rho_prev if rho_init is None else rho_init)
@@ -151,10 +171,10 @@ class MPC(Module):
             rho = self.rho_prev if rho_init is None else rho_init
             prev = None if self.just_initialized else self._device_history()
             persistent = (PERSISTENT_SOLVE and x.size(0) <= PERSISTENT_SOLVE_MAX_BATCH
-                          and al_utils.fused_solve_supported(x.size(0), dx, self.T, strided))
+                          and al_utils.fused_solve_supported(x.size(0), dx, self.T, strided, xb))
             xu, hc, hl, hr, resn, fail = al_utils.ALSolveDevice.apply(          # the iterate enters detached (AL_mpc.py:287)
                 x.detach(), u.detach(), x0.detach(), cost.C.to(dt), cost.c.to(dt), lamda.detach(), rho.detach(), dx,
-                self.u_lower, self.u_upper, self.al_iter, prev, persistent)
+                self.u_lower, self.u_upper, self.al_iter, prev, persistent, self.x_lower, self.x_upper)
             self.fail_log.append(fail)          # per-AL-iteration Cholesky-failure flags of the calls since reinitialize()
             if CHECK_CHOLESKY and bool(fail.any()):
                 # a Cholesky factorisation broke down somewhere in the batch: the reference then switches the batch to an
@@ -204,14 +224,14 @@ class MPC(Module):
                 # registered device model: the four Newton steps in one C-ABI call (dqp_al_newton_solve);
                 # Cholesky-failure flags are collected and checked once after the last AL iteration
                 out, status = al_utils.NewtonALDevice.apply(xu, x0, lamda, rho, Q, q, dx, self.u_lower,
-                                                            self.u_upper, general, fail_flags)
+                                                            self.u_upper, general, fail_flags, self.x_lower, self.x_upper)
             else:
                 out, status = general(Q, q)
             x, u = out[:, :, :self.n_state], out[:, :, self.n_state:]
             with torch.no_grad():
                 if device_path and torch.is_tensor(rho):
                     lamda, cost_res, dyn_res_clamp = al_utils.outer_update_device(
-                        out, x0, lamda, rho, Q, q, dx, self.u_lower, self.u_upper)
+                        out, x0, lamda, rho, Q, q, dx, self.u_lower, self.u_upper, self.x_lower, self.x_upper)
                 else:
                     res, res_clamp = self.dyn_res(torch.cat((x, u), dim=2), dx, x0, res_type='both')
                     lamda = lamda + rho * res                                 # AL_mpc.py:299
@@ -259,7 +279,7 @@ class MPC(Module):
         return al_utils.dyn_res_eq(x, u, dx, x0)
 
     def dyn_res_ineq(self, x, u, dx, x0):
-        """AL_mpc.py:357-383: (res, res_clamp) of the control bounds."""
+        """AL_mpc.py:357-383: (res, res_clamp) of the control bounds, followed by the state bounds' rows where set."""
         return al_utils.dyn_res_ineq(x, u, x0, self.x_lower, self.x_upper, self.u_lower, self.u_upper)
 
     def rollout_lin(self, x, actions, F, f):

@@ -161,9 +161,13 @@ def dyn_res_eq(x, u, dx, x0):
 
 
 def dyn_res_ineq(x, u, x0, x_lower, x_upper, u_lower, u_upper):
-    """per knot [u - u_upper, u_lower - u]; clamp at 0 for the penalty term (al_utils.py:266-291)."""
+    """per knot [u - u_upper, u_lower - u]; clamp at 0 for the penalty term (al_utils.py:266-291).  With state bounds
+    the state rows -- knot-major, per knot [x - x_upper, x_lower - x], all T knots -- are appended behind the control
+    rows (the reference left them commented out, al_utils.py:272-280): (2 T m + 2 T n) rows."""
     B = x.shape[0]
     res = torch.cat((u - u_upper, u_lower - u), dim=2).reshape(B, -1)
+    if x_lower is not None:
+        res = torch.cat((res, torch.cat((x - x_upper, x_lower - x), dim=2).reshape(B, -1)), dim=1)
     return res, res.clamp(min=0)
 
 
@@ -175,8 +179,9 @@ def dyn_res(xu, dx, x0, x_lower=None, x_upper=None, u_lower=None, u_upper=None):
     return torch.cat((eq, iq), 1), torch.cat((eq, iqc), 1)
 
 
-def constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper):
-    """Residuals and the dense constraint Jacobian (al_utils.py:162-186,212-318).
+def constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper, x_lower=None, x_upper=None):
+    """Residuals and the dense constraint Jacobian (al_utils.py:162-186,212-318).  With state bounds 2 T n rows more,
+    behind the control rows: per knot +I / -I on the knot's x columns.
 
     Returns res, res_clamp (B,ncon) and J, Jc (B,ncon,nz); Jc has the rows of inactive
     inequalities (res_clamp == 0) zeroed.  Row/column order as in the reference: equality rows
@@ -190,10 +195,10 @@ def constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper):
     Jx = Jx.reshape(B, T - 1, n, n)
     Ju = Ju.reshape(B, T - 1, n, m)
     eq = torch.cat((x[:, 1:] - x_next.view(B, T - 1, n), x[:, :1] - x0[:, None]), 1).reshape(B, -1)
-    iq, iqc = dyn_res_ineq(x, u, x0, None, None, u_lower, u_upper)
+    iq, iqc = dyn_res_ineq(x, u, x0, x_lower, x_upper, u_lower, u_upper)
 
     neq, nineq, nz = T * n, 2 * T * m, T * nt
-    J = xu.new_zeros(B, neq + nineq, nz)
+    J = xu.new_zeros(B, neq + iq.shape[1], nz)
     Jeq = J[:, :neq].view(B, T, n, T, nt)
     ar = torch.arange(T - 1, device=xu.device)
     Jeq[:, ar, :, ar, :n] = -Jx.permute(1, 0, 2, 3)            # -df/dx_t
@@ -201,11 +206,15 @@ def constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper):
     eye_n = torch.eye(n, dtype=xu.dtype, device=xu.device)
     Jeq[:, ar, :, ar + 1, :n] = eye_n                          # +I on x_{t+1}
     Jeq[:, T - 1, :, 0, :n] = eye_n                            # x_0 - x0
-    Jiq = J[:, neq:].view(B, T, 2, m, T, nt)
+    Jiq = J[:, neq:neq + nineq].view(B, T, 2, m, T, nt)
     at = torch.arange(T, device=xu.device)
     eye_m = torch.eye(m, dtype=xu.dtype, device=xu.device)
     Jiq[:, at, 0, :, at, n:] = eye_m
     Jiq[:, at, 1, :, at, n:] = -eye_m
+    if x_lower is not None:
+        Jxb = J[:, neq + nineq:].view(B, T, 2, n, T, nt)
+        Jxb[:, at, 0, :, at, :n] = eye_n
+        Jxb[:, at, 1, :, at, :n] = -eye_n
     Jc = J.clone()
     Jc[:, neq:] *= (iqc > 0).to(xu.dtype)[..., None]
     return torch.cat((eq, iq), 1), torch.cat((eq, iqc), 1), J, Jc
@@ -215,7 +224,7 @@ def constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper):
 # that use them directly; the solver path goes through assemble_jacobian / the fused kernels
 def constraint_res_jac2(xu, x0, dx_jac, x_lower, x_upper, u_lower, u_upper):
     """-> (res, res_clamp, constraint_jac, constraint_jac_clamp, constraint_hess) as al_utils.py:162-185."""
-    res, resc, J, Jc = constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper)
+    res, resc, J, Jc = constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper, x_lower, x_upper)
     return res, resc, J, Jc, torch.bmm(Jc.transpose(1, 2), Jc)
 
 
@@ -233,7 +242,8 @@ def dyn_res_eq_jac(x, u, dx_jac, x0):
 
 
 def dyn_res_ineq_jac(x, u, x0, x_lower, x_upper, u_lower, u_upper):
-    """-> (res, res_clamp, jac, jac_clamp) of the control-bound rows (al_utils.py:294-318)."""
+    """-> (res, res_clamp, jac, jac_clamp) of the control-bound rows (al_utils.py:294-318), with state bounds followed
+    by the state rows (dyn_res_ineq)."""
     B, T, n = x.shape
     m = u.shape[-1]
     res, resc = dyn_res_ineq(x, u, x0, x_lower, x_upper, u_lower, u_upper)
@@ -243,13 +253,19 @@ def dyn_res_ineq_jac(x, u, x0, x_lower, x_upper, u_lower, u_upper):
     J[:, at, 0, :, at, n:] = eye_m
     J[:, at, 1, :, at, n:] = -eye_m
     J = J.reshape(B, 2 * T * m, T * (n + m))
+    if x_lower is not None:
+        Jx = x.new_zeros(B, T, 2, n, T, n + m)
+        eye_n = torch.eye(n, dtype=x.dtype, device=x.device)
+        Jx[:, at, 0, :, at, :n] = eye_n
+        Jx[:, at, 1, :, at, :n] = -eye_n
+        J = torch.cat((J, Jx.reshape(B, 2 * T * n, T * (n + m))), dim=1)
     return res, resc, J, J * (resc > 0).to(x.dtype)[..., None]
 
 
 def merit_hessian(xu, Q, q, dx_jac, x0, lamda, rho, x_lower, x_upper, u_lower, u_upper, diag_cost=True):
     """diag(Q) + rho Jc^T Jc, dense (B, nz, nz)   (al_utils.py:105-119)."""
     B = xu.shape[0]
-    _, _, _, Jc = constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper)
+    _, _, _, Jc = constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper, x_lower, x_upper)
     Qfull = torch.diag_embed(Q.reshape(B, -1)) if diag_cost else Q
     return Qfull + rho.reshape(B, 1, 1) * torch.bmm(Jc.transpose(1, 2), Jc)
 
@@ -268,7 +284,8 @@ def compute_cost_gradient(xu, Q, q, diag_cost=True):
 
 def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_upper, diag_cost=True):
     """cost + rho/2 |res_clamp|^2 + lamda . res; a leading candidate axis (n_ls,B,T,nt) is
-    folded into the batch (al_utils.py:37-59)."""
+    folded into the batch (al_utils.py:37-59).  With state bounds the torch ops below run (dqp_al_merit has the fixed
+    row order without state rows)."""
     m_ctrl = xu.shape[-1] - x0.shape[-1]
     if (xu.is_cuda and not torch.is_grad_enabled() and x_lower is None and x_upper is None
             and bounds_supported(u_lower, u_upper, x0.shape[0], xu.shape[-2], m_ctrl)    # a layout the kernel takes
@@ -284,6 +301,8 @@ def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_up
             u_lower = rep(u_lower)
         if per_sample(u_upper):
             u_upper = rep(u_upper)
+        if per_sample(x_lower):
+            x_lower, x_upper = rep(x_lower), rep(x_upper)
     B = xu.shape[0]
     res, resc = dyn_res(xu, dx, x0, x_lower, x_upper, u_lower, u_upper)
     return compute_cost(xu, Q, q) + 0.5 * rho[:, 0] * (resc * resc).sum(1) + (lamda * res).sum(1)
@@ -323,8 +342,16 @@ class HessianTerms:
 
 def merit_grad_hessian(xu, Q, q, dx, dx_jac, x0, lamda, rho, x_lower, x_upper, u_lower, u_upper,
                        diag_cost=True):
-    """grad = Q xu + q + J^T lamda + rho Jc^T res_clamp ; Hessian terms (al_utils.py:62-102)."""
+    """grad = Q xu + q + J^T lamda + rho Jc^T res_clamp ; Hessian terms (al_utils.py:62-102).  With state bounds the
+    Jacobian comes from constraint_jacobian (dqp_al_assemble has the fixed row order without state rows)."""
     B = xu.shape[0]
+    if x_lower is not None:
+        _, resc, J, Jc = constraint_jacobian(xu, x0, dx_jac, u_lower, u_upper, x_lower, x_upper)
+        J, Jc, resc = J.detach(), Jc.detach(), resc.detach()
+        gterm = (torch.bmm(lamda[:, None, :].to(J.dtype), J)
+                 + rho.reshape(B, 1, 1).to(J.dtype) * torch.bmm(resc[:, None, :], Jc))[:, 0]
+        grad = compute_cost_gradient(xu, Q, q, diag_cost).reshape(B, -1) + gterm.to(xu.dtype)
+        return grad, HessianTerms(Jc, Q.reshape(B, -1), rho)
     Jc, gterm = assemble_jacobian(xu, x0, dx_jac, lamda, rho, u_lower, u_upper)
     grad = compute_cost_gradient(xu, Q, q, diag_cost).reshape(B, -1) + gterm.to(xu.dtype)
     return grad, HessianTerms(Jc, Q.reshape(B, -1), rho)
@@ -549,7 +576,7 @@ class NewtonALDevice(torch.autograd.Function):
     LU solve (al_utils.py:419-427)."""
 
     @staticmethod
-    def forward(ctx, xi, x0, lam, rho, Q, q, dyn, u_lower, u_upper, slow, fail_sink=None):
+    def forward(ctx, xi, x0, lam, rho, Q, q, dyn, u_lower, u_upper, slow, fail_sink=None, x_lower=None, x_upper=None):
         lib = _lib.load()
         B, T, nt = xi.shape
         n, m = dyn.n_state, dyn.n_ctrl
@@ -568,8 +595,14 @@ class NewtonALDevice(torch.autograd.Function):
         status = torch.empty(B, **kw)
         fail = torch.zeros(1, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_newton_solve_bytes(ctypes.byref(dims), banded)) // 8 + 1, **kw)
-        _lib.call("dqp_al_newton_solve_bounds", dev, dims, dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded, *keep, bd.ref(),
-                  xu, L, status, fail, ws)
+        if x_lower is not None:     # state bounds: the block-tridiagonal form with the state rows (lam: ncon_x columns)
+            assert banded, "state bounds run on the block-tridiagonal kernels only"
+            xbd = bounds_layout(x_lower, x_upper, B, T, n)
+            _lib.call("dqp_al_newton_solve_xbounds", dev, dims, dyn.id, dyn.dt, MAX_NEWTON_STEPS, *keep, bd.ref(), xbd.ref(),
+                      xu, L, status, fail, ws)
+        else:
+            _lib.call("dqp_al_newton_solve_bounds", dev, dims, dyn.id, dyn.dt, MAX_NEWTON_STEPS, banded, *keep, bd.ref(),
+                      xu, L, status, fail, ws)
         ctx.slow_ctx = None
         if fail_sink is not None:           # the caller checks all flags once, at the end of its solve
             fail_sink.append(fail)
@@ -588,13 +621,13 @@ class NewtonALDevice(torch.autograd.Function):
         if ctx.slow_ctx is not None:
             out, Qs, qs = ctx.slow_ctx
             gQ, gq = torch.autograd.grad(out, (Qs, qs), x_grad)
-            return (None,) * 4 + (gQ, gq) + (None,) * 5
+            return (None,) * 4 + (gQ, gq) + (None,) * 7
         L, x = ctx.saved_tensors
         if ctx.banded:
             g = _banded_solve(ctx.dims, ctx.dyn_id, L, x_grad).to(x_grad.dtype)
         else:
             g = chol_solve_neg(L, x_grad).reshape(x_grad.shape).to(x_grad.dtype)
-        return (None,) * 4 + (g * x.to(x_grad.dtype), g) + (None,) * 5      # al_utils.py:482-485
+        return (None,) * 4 + (g * x.to(x_grad.dtype), g) + (None,) * 7      # al_utils.py:482-485
 
 
 class ALSolveDevice(torch.autograd.Function):
@@ -604,14 +637,17 @@ class ALSolveDevice(torch.autograd.Function):
     the previous call or None.  Returns xu (B,T,nt) and, non-differentiable, the new history (cost (K,B), lam
     (K,B,ncon), rho (K,B)), |res_clamp| (B) and the per-AL-iteration Cholesky-failure flags (int32).
     `fused`: the single-launch entry dqp_al_mpc_solve_fused (small batches; fused_solve_supported says where it
-    exists) instead of the launch train -- the same arguments, outputs and backward."""
+    exists) instead of the launch train -- the same arguments, outputs and backward.
+    `x_lower` / `x_upper`: state bounds (dqp_al_mpc_solve_xbounds; the launch train only): lam, the history rows and
+    `prev` then have dqp_al_ncon_xbounds columns.  Enqueue-only like the call without them."""
 
     @staticmethod
-    def forward(ctx, x_init, u_init, x0, Q, q, lam, rho, dyn, u_lower, u_upper, al_iter, prev, fused=False):
+    def forward(ctx, x_init, u_init, x0, Q, q, lam, rho, dyn, u_lower, u_upper, al_iter, prev, fused=False,
+                x_lower=None, x_upper=None):
         lib = _lib.load()
         B, T, n = x_init.shape
         m = u_init.shape[-1]
-        nt, ncon = n + m, T * n + 2 * T * m
+        nt, ncon = n + m, lam.shape[-1]         # T n + 2 T m, with state bounds + 2 T n
         dev = x0.device
         d64 = lambda t: t.detach().double().contiguous()
         keep = [d64(x_init), d64(u_init), d64(x0), d64(Q), d64(q)]
@@ -627,9 +663,16 @@ class ALSolveDevice(torch.autograd.Function):
         L = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), dyn.id)) // 8, **kw)
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8 + 1, **kw)
-        _lib.call("dqp_al_mpc_solve_fused_bounds" if fused else "dqp_al_mpc_solve_bounds", dev, dims, dyn.id, dyn.dt,
-                  al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn, L, status,
-                  fail, ws)
+        if x_lower is not None:
+            assert not fused and ncon == T * n + 2 * T * m + 2 * T * n
+            xbd = bounds_layout(x_lower, x_upper, B, T, n)
+            _lib.call("dqp_al_mpc_solve_xbounds", dev, dims, dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(),
+                      xbd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn, L, status, fail, ws)
+        else:
+            assert ncon == T * n + 2 * T * m
+            _lib.call("dqp_al_mpc_solve_fused_bounds" if fused else "dqp_al_mpc_solve_bounds", dev, dims, dyn.id, dyn.dt,
+                      al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn, L, status,
+                      fail, ws)
         ctx.dims, ctx.dyn_id = dims, dyn.id
         ctx.save_for_backward(L, xu)
         ctx.mark_non_differentiable(hc, hl, hr, resn, fail)
@@ -639,12 +682,15 @@ class ALSolveDevice(torch.autograd.Function):
     def backward(ctx, x_grad, *unused):
         L, x = ctx.saved_tensors
         g = _banded_solve(ctx.dims, ctx.dyn_id, L, x_grad)
-        return (None,) * 3 + (g * x, g) + (None,) * 8                      # al_utils.py:482-485
+        return (None,) * 3 + (g * x, g) + (None,) * 10                     # al_utils.py:482-485
 
 
-def fused_solve_supported(n_batch, dyn, T, strided=False):
+def fused_solve_supported(n_batch, dyn, T, strided=False, state_bounds=False):
     """dqp_al_mpc_solve_fused exists for this registered model and horizon (n_state + n_ctrl <= 8, 2 <= T <= 32);
-    `strided`: with per-sample / per-knot bounds, whose 2 T n_ctrl doubles are staged in LDS next to the problem"""
+    `strided`: with per-sample / per-knot bounds, whose 2 T n_ctrl doubles are staged in LDS next to the problem.
+    `state_bounds`: False -- the single-launch solve has no state rows."""
+    if state_bounds:
+        return False
     dims = _lib.dqp_al_mpc_dims(n_batch, dyn.n_state, dyn.n_ctrl, T)
     if strided:
         m = dyn.n_ctrl
@@ -653,8 +699,9 @@ def fused_solve_supported(n_batch, dyn, T, strided=False):
     return bool(_lib.load().dqp_al_mpc_solve_fused_supported(ctypes.byref(dims), dyn.id))
 
 
-def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper):
-    """AL_mpc.py:296-307 in one launch (dqp_al_outer_update): -> (lam_new, cost (B), |res_clamp| (B))."""
+def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper, x_lower=None, x_upper=None):
+    """AL_mpc.py:296-307 in one launch (dqp_al_outer_update): -> (lam_new, cost (B), |res_clamp| (B)).  With state
+    bounds dqp_al_outer_update_xbounds: lam has the state rows' columns too."""
     lib = _lib.load()
     B, T, nt = xu.shape
     dev = xu.device
@@ -664,7 +711,11 @@ def outer_update_device(xu, x0, lam, rho, Q, q, dyn, u_lower, u_upper):
     kw = dict(dtype=torch.float64, device=dev)
     lam_new, cost, resn = torch.empty_like(keep[2]), torch.empty(B, **kw), torch.empty(B, **kw)
     dims = _lib.dqp_al_mpc_dims(B, dyn.n_state, dyn.n_ctrl, T)
-    _lib.call("dqp_al_outer_update_bounds", dev, dims, dyn.id, dyn.dt, *keep, bd.ref(), lam_new, cost, resn)
+    if x_lower is not None:
+        xbd = bounds_layout(x_lower, x_upper, B, T, dyn.n_state)
+        _lib.call("dqp_al_outer_update_xbounds", dev, dims, dyn.id, dyn.dt, *keep, bd.ref(), xbd.ref(), lam_new, cost, resn)
+    else:
+        _lib.call("dqp_al_outer_update_bounds", dev, dims, dyn.id, dyn.dt, *keep, bd.ref(), lam_new, cost, resn)
     return lam_new.to(lam.dtype), cost.to(xu.dtype), resn.to(xu.dtype)
 
 

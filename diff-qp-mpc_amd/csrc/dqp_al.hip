@@ -36,6 +36,8 @@ namespace {
 
 using dqp::StridedBounds;
 using dqp::strided_bounds;
+using dqp::BoxBounds;
+using dqp::box_bounds;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -648,7 +650,11 @@ struct LsAP {
 // + the bound layout (dqp_al_bounds.h): the argument of the StridedBounds<> instantiations, and what the host code
 // carries; a vector instantiation is launched with the LsAP part of it
 struct LsAPS : LsAP { long long bsb, bst; };
-template <class Map> using LsArg = std::conditional_t<strided_bounds<Map>::value, LsAPS, LsAP>;
+// + the state box (dqp_al_bounds.h: BoxBounds<>): the argument of the BoxBounds<> instantiations, and what the host code
+// carries (xlo == NULL: no state box); the other instantiations keep their argument types and sizes
+struct LsAPX : LsAPS { const double *xlo, *xhi; long long xsb, xst; };
+template <class Map> using LsArg =
+    std::conditional_t<box_bounds<Map>::value, LsAPX, std::conditional_t<strided_bounds<Map>::value, LsAPS, LsAP>>;
 
 // merit (al_utils.py:37-59) of ncand candidates xu + 2^-k upd per problem (x_0 pinned to x0,
 // al_utils.py:515), dynamics evaluated in the kernel; 16 lanes per (candidate, problem).  ncand = 0
@@ -662,7 +668,8 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     __shared__ double ls_lds[16 * 17 * ZS];
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m;
+    constexpr bool XB = box_bounds<Map>::value;
+    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0);
     const int nc = P.ncand > 0 ? P.ncand : 1;
     const int slot = threadIdx.x >> 4, r = threadIdx.x & 15;
     const long long item = (long long)blockIdx.x * 16 + slot;
@@ -695,6 +702,11 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
                     else { uut = P.uu[i]; ult = P.ul[i]; }
                     const double hi = z - uut, lo = ult - z;
                     acc += lam[row] * hi + lam[row + m] * lo +
+                           0.5 * rho * (fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
+                } else if constexpr (XB) {      // the state rows of the element, into the same accumulator
+                    const int row = neq + 2 * T * m + t * 2 * n + j;
+                    const double hi = z - P.xhi[b * P.xsb + t * P.xst + j], lo = P.xlo[b * P.xsb + t * P.xst + j] - z;
+                    acc += lam[row] * hi + lam[row + n] * lo +
                            0.5 * rho * (fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
                 }
             }
@@ -761,7 +773,8 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     constexpr int EPL = (TMAX * nt + TPI - 1) / TPI;       // elements of the (T, nt) arrays per lane, T <= TMAX
     extern __shared__ double lsg_lds[];
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m, nzq = T * nt;
+    constexpr bool XB = box_bounds<Map>::value;
+    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0), nzq = T * nt;
     const int nc = P.ncand > 0 ? P.ncand : 1;
     const int grp = threadIdx.x / TPI, r = threadIdx.x % TPI;
     const long long pb = (long long)blockIdx.x * (256 / TPI) + grp;
@@ -783,6 +796,12 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     constexpr bool POLY = EPL >= 12;
     double ex[EPL], eu[EPL], eq[POLY ? 1 : EPL], el[POLY ? 1 : EPL];
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+    // state box: the pair and the two multipliers of the lane's state elements, loaded once with the element (short
+    // knots); the long knots, whose registers are taken, read them per candidate (20 reads of lines that stay in cache)
+    constexpr bool XREG = XB && !POLY;
+    [[maybe_unused]] double sh[XREG ? EPL : 1], sl[XREG ? EPL : 1], smu[XREG ? EPL : 1], sml[XREG ? EPL : 1];
+    [[maybe_unused]] const double *xhb = nullptr, *xlb = nullptr;
+    if constexpr (XB) { xhb = P.xhi + b * P.xsb; xlb = P.xlo + b * P.xsb; }
 #pragma unroll
     for (int i = 0; i < EPL; ++i) {
         const int e = r + TPI * i, ec = e < nzq ? e : 0, t = ec / nt, j = ec - t * nt;
@@ -797,6 +816,12 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
             c2 += 0.5 * qd * eu[i] * eu[i];
         } else {
             eq[i] = qd; el[i] = ql;
+        }
+        if constexpr (XREG) {
+            const bool xs = ok && j < n;
+            const int jx = xs ? j : 0, row = neq + 2 * T * m + t * 2 * n + jx;
+            sh[i] = xs ? xhb[t * P.xst + jx] : INFINITY; sl[i] = xs ? xlb[t * P.xst + jx] : -INFINITY;
+            smu[i] = xs ? lam[row] : 0.0; sml[i] = xs ? lam[row + n] : 0.0;
         }
     }
     double cx[UPL], cu[UPL], lu[UPL], ll[UPL], hi[UPL], lo[UPL];
@@ -838,6 +863,18 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
                 const double z = fma(step, eu[i], ex[i]);
                 zb[t * ZS + j] = z;
                 if constexpr (!POLY) acc += (0.5 * eq[i] * z + el[i]) * z;
+                if constexpr (XB) {         // the element's state rows, into the accumulator the lane already owns
+                    if (j < n) {
+                        double h, l, mu, ml;
+                        if constexpr (XREG) { h = sh[i]; l = sl[i]; mu = smu[i]; ml = sml[i]; }
+                        else {
+                            const int row = neq + 2 * T * m + t * 2 * n + j;
+                            h = xhb[t * P.xst + j]; l = xlb[t * P.xst + j]; mu = lam[row]; ml = lam[row + n];
+                        }
+                        const double vh = z - h, vl = l - z;
+                        acc += mu * vh + ml * vl + 0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
+                    }
+                }
             }
         }
 #pragma unroll
@@ -891,7 +928,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     }
 }
 
-template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPS &P, hipStream_t st)
+template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPX &P, hipStream_t st)
 {
     constexpr int ZS = (Map::NX + Map::NU) | 1, G = 256 / TPI;
     constexpr bool POLY = (TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12;
@@ -904,7 +941,7 @@ template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPS &P
     return (P.xu_w && split == 1 && P.ncand > 0) ? 2 : DQP_OK;     // 2: the selection happened in the kernel
 }
 
-template <class Map> int launch_ls_t(const LsAPS &P, hipStream_t st)
+template <class Map> int launch_ls_t(const LsAPX &P, hipStream_t st)
 {
     // the model phase keeps T - 1 lanes of a group busy: four lanes for the shortest horizons (config 5: T = 5)
     if (P.T <= 5) return launch_ls_group<Map, 4, 5>(P, st);
@@ -916,12 +953,13 @@ template <class Map> int launch_ls_t(const LsAPS &P, hipStream_t st)
     return DQP_OK;
 }
 
-template <class Model> int launch_ls_layout(const LsAPS &P, hipStream_t st)
+template <class Model> int launch_ls_layout(const LsAPX &P, hipStream_t st)
 {
+    if (P.xlo) return launch_ls_t<BoxBounds<Model>>(P, st);         // a state box: both boxes strided
     return (P.bsb != 0 || P.bst != 0) ? launch_ls_t<StridedBounds<Model>>(P, st) : launch_ls_t<Model>(P, st);
 }
 
-int launch_ls(const LsAPS &P, hipStream_t st)
+int launch_ls(const LsAPX &P, hipStream_t st)
 {
     return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
         return launch_ls_layout<typename decltype(model)::Map>(P, st);
@@ -935,6 +973,8 @@ struct OutP {
     int B, n, m, T, dyn;
     double *rho_next;       // optional: rho * 10 (AL_mpc.py:307), for the next AL iteration of dqp_al_mpc_solve
     long long bsb, bst;     // bound layout (dqp_al_bounds.h), read by the StridedBounds<> instantiations only
+    const double *xlo, *xhi;    // state box, read by the BoxBounds<> instantiations only (else NULL); lam / lam_new then
+    long long xsb, xst;         // carry 2 T n more rows
 };
 
 // Between two AL iterations (qpth/AL_mpc.py:296-307): res = constraint residual at the new iterate,
@@ -944,7 +984,8 @@ template <class Map>
 __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m;
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m;
+    constexpr bool XB = box_bounds<Map>::value;
+    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0);
     const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int r = threadIdx.x & 15;
     const long long b = item < P.B ? item : P.B - 1;
@@ -984,6 +1025,17 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
             if (live) {
                 ln[row] = fmax(lam[row] + rho * hi, 0.0);               // AL_mpc.py:300-301
                 ln[row + m] = fmax(lam[row + m] + rho * lo, 0.0);
+            }
+        }
+        if constexpr (XB) {         // the knot's state rows: multipliers clamped at 0, their share of |res_clamp|
+            for (int j = 0; j < n; ++j) {
+                const double hi = z[j] - P.xhi[b * P.xsb + t * P.xst + j], lo = P.xlo[b * P.xsb + t * P.xst + j] - z[j];
+                const int row = neq + 2 * T * m + t * 2 * n + j;
+                rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
+                if (live) {
+                    ln[row] = fmax(lam[row] + rho * hi, 0.0);
+                    ln[row + n] = fmax(lam[row + n] + rho * lo, 0.0);
+                }
             }
         }
     }
@@ -1043,13 +1095,52 @@ __global__ __launch_bounds__(256) void al_start_kernel(StartP P)
     for (int e = r; e < ncon; e += 16) l0[e] = P.K > 0 ? lam[e] * scale : lam[e];
     if (r == 0) { P.cost0[b] = cost0; P.rho0[b] = rho; }
 }
+// The same with a state box: the multipliers and the history rows are 2 T n wider, and the norms and the scaling of the warm
+// start run over all of them.  A kernel of its own, so that al_start_kernel stays the code it was.
+__global__ __launch_bounds__(256) void al_start_xbounds_kernel(StartP P)
+{
+    const int n = P.n, m = P.m, nt = n + m, T = P.T, ncon = T * n + 2 * T * m + 2 * T * n;
+    const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int r = threadIdx.x & 15;
+    const long long b = item < P.B ? item : P.B - 1;
+    const bool live = item < P.B;
+    if (blockIdx.x == 0 && (int)threadIdx.x < P.nfail) P.fail[threadIdx.x] = 0;
+    double *xu = P.xu + b * (long long)T * nt;
+    const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
+    double quad = 0.0, lin = 0.0;
+    for (int e = r; e < T * nt; e += 16) {
+        const int t = e / nt, j = e - t * nt;
+        const double v = j < n ? P.x_init[(b * T + t) * n + j] : P.u_init[(b * T + t) * m + (j - n)];
+        if (live) xu[e] = v;
+        quad += v * Qd[e] * v;
+        lin += q[e] * v;
+    }
+    const double cost0 = 0.5 * dqp::r16::row_sum(quad) + dqp::r16::row_sum(lin);       // al_utils.compute_cost, diagonal cost
+    const double *lam = P.lam_in + b * (long long)ncon;
+    double scale = 1.0, rho = P.rho_in[b];
+    if (P.K > 0) {
+        int pick = P.K - 1;                                   // torch.max of an all-False column: index 0 = the newest
+        for (int k = P.K - 1; k >= 0; --k)
+            if (P.hist_cost[(long long)k * P.B + b] < cost0) { pick = k; break; }
+        const double *lh = P.hist_lam + ((long long)pick * P.B + b) * ncon;
+        double nh = 0.0, nl = 0.0;
+        for (int e = r; e < ncon; e += 16) { nh += lh[e] * lh[e]; nl += lam[e] * lam[e]; }
+        scale = sqrt(dqp::r16::row_sum(nh)) / sqrt(dqp::r16::row_sum(nl));
+        rho = P.hist_rho[(long long)pick * P.B + b];
+    }
+    if (!live) return;
+    double *l0 = P.lam0 + b * (long long)ncon;
+    for (int e = r; e < ncon; e += 16) l0[e] = P.K > 0 ? lam[e] * scale : lam[e];
+    if (r == 0) { P.cost0[b] = cost0; P.rho0[b] = rho; }
+}
 
 int launch_outer(const OutP &P, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.B + 15) / 16)), block(256);
     return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
         using Map = typename decltype(model)::Map;
-        if (P.bsb != 0 || P.bst != 0) DQP_LAUNCH(al_outer_kernel<StridedBounds<Map>>, grid, block, 0, st, P);
+        if (P.xlo) DQP_LAUNCH(al_outer_kernel<BoxBounds<Map>>, grid, block, 0, st, P);
+        else if (P.bsb != 0 || P.bst != 0) DQP_LAUNCH(al_outer_kernel<StridedBounds<Map>>, grid, block, 0, st, P);
         else DQP_LAUNCH(al_outer_kernel<Map>, grid, block, 0, st, P);
         return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
     });
@@ -1213,7 +1304,8 @@ __attribute__((visibility("default"))) size_t dqp_al_newton_solve_bytes(const dq
 static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
                              const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
                              const dqp_al_bounds *bounds, double *xu, double *L, double *status,
-                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor = true);
+                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor = true,
+                             const dqp_al_bounds *xb = nullptr);
 
 __attribute__((visibility("default"))) int
 dqp_al_newton_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
@@ -1236,11 +1328,13 @@ dqp_al_newton_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_s
                                       workspace, stream);
 }
 
-// clear_fail = false: the caller's own kernel zeroed the flag (dqp_al_mpc_solve: al_start_kernel clears all of them)
+// clear_fail = false: the caller's own kernel zeroed the flag (dqp_al_mpc_solve: al_start_kernel clears all of them);
+// xb: the state box of the `_xbounds` entries (block-tridiagonal form only; the caller checked its layout), else NULL
 static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
                              const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
                              const dqp_al_bounds *bounds, double *xu, double *L, double *status,
-                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor)
+                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor,
+                             const dqp_al_bounds *xb)
 {
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || n_steps < 1) return DQP_ERR_BAD_ARG;
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
@@ -1249,6 +1343,9 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
     const double *u_lower = bounds->lower, *u_upper = bounds->upper;
     const long long bsb = bounds->stride_b, bst = bounds->stride_t;
     if (!x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !xu || !fail || !workspace) return DQP_ERR_BAD_ARG;
+    if (xb && (!xb->lower || !xb->upper || !banded)) return DQP_ERR_BAD_ARG;
+    const double *xlo = xb ? xb->lower : nullptr, *xhi = xb ? xb->upper : nullptr;
+    const long long xsb = xb ? xb->stride_b : 0, xst = xb ? xb->stride_t : 0;
     const int B = d->nbatch, n = d->n_state, m = d->n_ctrl, T = d->T, nt = n + m, nz = T * nt;
     const int ncon = T * n + 2 * T * m;
     hipStream_t st = (hipStream_t)stream;
@@ -1263,16 +1360,17 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
         double *merit_cur = w;     w += (size_t)B;
         int32_t *info = (int32_t *)w;
         if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-        LsAPS Lp = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst};
+        LsAPX Lp = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst},
+                    xlo, xhi, xsb, xst};
         int rc0 = launch_ls(Lp, st);                                    // merit at the start
         if (rc0) return rc0;
         for (int it = 0; it < n_steps; ++it) {
             // only the last step's factor is used afterwards (NewtonAL.backward, al_utils.py:477-480)
             int rc = dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, upd, L, info,
-                                                            stream, (it == n_steps - 1 && keep_factor) ? 1 : 0);
+                                                            stream, (it == n_steps - 1 && keep_factor) ? 1 : 0, xb);
             if (rc) return rc;
-            LsAPS Lc = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id,
-                         xu, merit_cur, status, fail, info}, bsb, bst};
+            LsAPX Lc = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id,
+                          xu, merit_cur, status, fail, info}, bsb, bst}, xlo, xhi, xsb, xst};
             rc = launch_ls(Lc, st);
             if (rc != DQP_OK && rc != 2) return rc;
             if (rc != 2) {          // candidates split over several groups: select in a launch of its own
@@ -1298,7 +1396,7 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
     double *merit_cur = w;     w += (size_t)B;
     int32_t *info = (int32_t *)w;
     if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-    LsAPS Lp = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst};
+    LsAPX Lp = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst}};
     rc = launch_ls(Lp, st);                                             // merit at the start
     if (rc) return rc;
     for (int it = 0; it < n_steps; ++it) {
@@ -1314,7 +1412,7 @@ static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, in
         P.Jc = Jc; P.Qd = Qdiag; P.rho = rho; P.grad = grad; P.update = upd; P.L = L; P.info = info;
         rc = launch_newton(P, lds, stream);
         if (rc) return rc;
-        LsAPS Lc = {{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id}, bsb, bst};
+        LsAPX Lc = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id}, bsb, bst}};
         rc = launch_ls(Lc, st);
         if (rc) return rc;
         SelP Se = {merit, upd, x0, xu, merit_cur, status, fail, info, B, n, nz, 20};
@@ -1334,10 +1432,11 @@ dqp_al_outer_update(const dqp_al_mpc_dims *d, int dyn_id, double dt, const doubl
     return dqp_al_outer_update_bounds(d, dyn_id, dt, xu, x0, lam, rho, Qdiag, q, &bd, lam_new, cost, res_norm, stream);
 }
 
-__attribute__((visibility("default"))) int
-dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
-                           const double *lam, const double *rho, const double *Qdiag, const double *q,
-                           const dqp_al_bounds *bounds, double *lam_new, double *cost, double *res_norm, void *stream)
+// xb: the state box of dqp_al_outer_update_xbounds (its layout checked by the caller), else NULL
+static int outer_update_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
+                             const double *lam, const double *rho, const double *Qdiag, const double *q,
+                             const dqp_al_bounds *bounds, const dqp_al_bounds *xb, double *lam_new, double *cost,
+                             double *res_norm, void *stream)
 {
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return DQP_ERR_BAD_ARG;
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
@@ -1347,9 +1446,59 @@ dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, cons
     if (d->n_state > 12 || d->n_state + d->n_ctrl > 16) return DQP_ERR_TOO_LARGE;
     if (!xu || !x0 || !lam || !rho || !Qdiag || !q || !u_lower || !u_upper || !lam_new || !cost || !res_norm)
         return DQP_ERR_BAD_ARG;
+    if (xb && (!xb->lower || !xb->upper)) return DQP_ERR_BAD_ARG;
     OutP P = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, lam_new, cost, res_norm, dt, d->nbatch, d->n_state,
-              d->n_ctrl, d->T, dyn_id, nullptr, (long long)bounds->stride_b, (long long)bounds->stride_t};
+              d->n_ctrl, d->T, dyn_id, nullptr, (long long)bounds->stride_b, (long long)bounds->stride_t,
+              xb ? xb->lower : nullptr, xb ? xb->upper : nullptr, xb ? (long long)xb->stride_b : 0,
+              xb ? (long long)xb->stride_t : 0};
     return launch_outer(P, (hipStream_t)stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
+                           const double *lam, const double *rho, const double *Qdiag, const double *q,
+                           const dqp_al_bounds *bounds, double *lam_new, double *cost, double *res_norm, void *stream)
+{
+    return outer_update_impl(d, dyn_id, dt, xu, x0, lam, rho, Qdiag, q, bounds, nullptr, lam_new, cost, res_norm, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_outer_update_xbounds(const dqp_al_mpc_dims *d, int model, double dt, const double *xu, const double *x0,
+                            const double *lam, const double *rho, const double *Qdiag, const double *q,
+                            const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *lam_new, double *cost,
+                            double *res_norm, void *stream)
+{
+    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
+    if (rc) return rc;
+    return outer_update_impl(d, model, dt, xu, x0, lam, rho, Qdiag, q, bounds, xbounds, lam_new, cost, res_norm, stream);
+}
+
+__attribute__((visibility("default"))) int32_t dqp_al_ncon_xbounds(const dqp_al_mpc_dims *d)
+{
+    if (!d || d->n_state <= 0 || d->n_ctrl <= 0 || d->T <= 0) return 0;
+    return d->T * d->n_state + 2 * d->T * d->n_ctrl + 2 * d->T * d->n_state;
+}
+
+// the workspace does not depend on the rows: that of the `_bounds` twins
+__attribute__((visibility("default"))) size_t dqp_al_newton_solve_xbounds_bytes(const dqp_al_mpc_dims *d)
+{
+    return dqp_al_newton_solve_bytes(d, 1);
+}
+__attribute__((visibility("default"))) size_t dqp_al_mpc_solve_xbounds_bytes(const dqp_al_mpc_dims *d)
+{
+    return dqp_al_newton_solve_bytes(d, 1);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_newton_solve_xbounds(const dqp_al_mpc_dims *d, int model, double dt, int32_t n_steps, const double *x0,
+                            const double *Qdiag, const double *q, const double *lam, const double *rho,
+                            const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *xu, double *L,
+                            double *status, int32_t *fail, void *workspace, void *stream)
+{
+    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
+    if (rc) return rc;
+    return newton_solve_impl(d, model, dt, n_steps, 1, x0, Qdiag, q, lam, rho, bounds, xu, L, status, fail, workspace,
+                             stream, true, true, xbounds);
 }
 
 __attribute__((visibility("default"))) size_t dqp_al_mpc_solve_bytes(const dqp_al_mpc_dims *d)
@@ -1371,13 +1520,13 @@ dqp_al_mpc_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_ite
                                    status, fail, workspace, stream);
 }
 
-__attribute__((visibility("default"))) int
-dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
-                        const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
-                        const dqp_al_bounds *bounds, const double *lam_in, const double *rho_in,
-                        const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
-                        double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
-                        double *status, int32_t *fail, void *workspace, void *stream)
+// xb: the state box of dqp_al_mpc_solve_xbounds (its layout checked by the caller), else NULL
+static int mpc_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                          const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
+                          const dqp_al_bounds *bounds, const dqp_al_bounds *xb, const double *lam_in, const double *rho_in,
+                          const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                          double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
+                          double *status, int32_t *fail, void *workspace, void *stream)
 {
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
         n_prev < 0)
@@ -1389,24 +1538,56 @@ dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t
         !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
         return DQP_ERR_BAD_ARG;
     if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
+    if (xb && (!xb->lower || !xb->upper)) return DQP_ERR_BAD_ARG;
     if (d->n_state > 12 || d->n_state + d->n_ctrl > 16) return DQP_ERR_TOO_LARGE;
     const int B = d->nbatch, n = d->n_state, m = d->n_ctrl, T = d->T;
-    const long long ncon = (long long)T * n + 2LL * T * m;
+    const long long ncon = (long long)T * n + 2LL * T * m + (xb ? 2LL * T * n : 0);
     hipStream_t st = (hipStream_t)stream;
     StartP S = {x_init, u_init, Qdiag, q, lam_in, rho_in, prev_cost, prev_lam, prev_rho, xu, hist_cost, hist_lam, hist_rho,
                 B, n, m, T, n_prev, fail, al_iter};
-    DQP_LAUNCH(al_start_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
+    if (xb) DQP_LAUNCH(al_start_xbounds_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
+    else DQP_LAUNCH(al_start_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
     for (int i = 0; i < al_iter; ++i) {
         const double *lam = hist_lam + (long long)i * B * ncon, *rho = hist_rho + (long long)i * B;
         int rc = newton_solve_impl(d, dyn_id, dt, newton_steps, 1, x0, Qdiag, q, lam, rho, bounds, xu, factor,
-                                   status, fail + i, workspace, stream, false, i == al_iter - 1);
+                                   status, fail + i, workspace, stream, false, i == al_iter - 1, xb);
         if (rc) return rc;
         OutP O = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, hist_lam + (long long)(i + 1) * B * ncon,
                   hist_cost + (long long)(i + 1) * B, res_norm, dt, B, n, m, T, dyn_id, hist_rho + (long long)(i + 1) * B,
-                  (long long)bounds->stride_b, (long long)bounds->stride_t};
+                  (long long)bounds->stride_b, (long long)bounds->stride_t,
+                  xb ? xb->lower : nullptr, xb ? xb->upper : nullptr, xb ? (long long)xb->stride_b : 0,
+                  xb ? (long long)xb->stride_t : 0};
         if ((rc = launch_outer(O, st)) != DQP_OK) return rc;
     }
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
+                        const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
+                        const dqp_al_bounds *bounds, const double *lam_in, const double *rho_in,
+                        const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
+                        double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
+                        double *status, int32_t *fail, void *workspace, void *stream)
+{
+    return mpc_solve_impl(d, dyn_id, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, bounds, nullptr, lam_in, rho_in,
+                          prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status,
+                          fail, workspace, stream);
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_xbounds(const dqp_al_mpc_dims *d, int model, double dt, int32_t al_iter, int32_t newton_steps,
+                         const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
+                         const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, const double *lam_in,
+                         const double *rho_in, const double *prev_cost, const double *prev_lam, const double *prev_rho,
+                         int32_t n_prev, double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
+                         double *factor, double *status, int32_t *fail, void *workspace, void *stream)
+{
+    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
+    if (rc) return rc;
+    return mpc_solve_impl(d, model, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, bounds, xbounds, lam_in, rho_in,
+                          prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status,
+                          fail, workspace, stream);
 }
 
 }  // extern "C"

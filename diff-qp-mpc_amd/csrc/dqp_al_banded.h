@@ -15,11 +15,11 @@ int al_banded_wide_newton(int n_state, int n_ctrl, const BandP &P, void *stream)
 int al_banded_wide_solve(int n_state, int n_ctrl, const BandP &P, void *stream);
 
 // dqp_al_banded.hip: dqp_al_banded_newton_step_bounds with `keep` = does the caller use this step's factor afterwards
-// (the Newton loop of dqp_al.hip keeps the last step's only)
+// (the Newton loop of dqp_al.hip keeps the last step's only); `xbounds`: the state box of the `_xbounds` entries, or NULL
 int al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
                                       const double *Qdiag, const double *q, const double *lam, const double *rho,
                                       const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info, void *stream,
-                                      int keep);
+                                      int keep, const dqp_al_bounds *xbounds = nullptr);
 
 }  // namespace dqp
 #endif

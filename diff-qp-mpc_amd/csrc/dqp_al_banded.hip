@@ -73,9 +73,12 @@ template <class Map> int run_newton(const BandP &P, void *stream)
     DQP_LAUNCH((al_banded_newton_kernel<Map, 16>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P BAND_STAMP_ARG);
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
-// the vector instantiation at (0, 0), the strided one otherwise
+// the vector instantiation at (0, 0), the strided one otherwise; with a state box the BoxBounds<> one (both boxes strided)
 template <class Map> int run_newton_layout(const BandP &P, void *stream)
 {
+    if constexpr (!is_given<Map>::value) {
+        if (P.xlo) return run_newton<BoxBounds<Map>>(P, stream);
+    }
     return (P.bsb != 0 || P.bst != 0) ? run_newton<StridedBounds<Map>>(P, stream) : run_newton<Map>(P, stream);
 }
 template <class Map> int run_solve(const BandP &P, void *stream)
@@ -138,16 +141,20 @@ __attribute__((visibility("default"))) size_t dqp_al_banded_jac_factor_bytes(con
 int dqp::al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
                                            const double *Qdiag, const double *q, const double *lam, const double *rho,
                                            const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info,
-                                           void *stream, int keep)
+                                           void *stream, int keep, const dqp_al_bounds *xbounds)
 {
     if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
     if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
     if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
+    if (xbounds && dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
     if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !update || !factor)
         return DQP_ERR_BAD_ARG;
+    if (xbounds && (!xbounds->lower || !xbounds->upper)) return DQP_ERR_BAD_ARG;
     BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, nullptr, nullptr, nullptr, update,
-               (double *)factor, info, dt, d->nbatch, d->T, keep, (long long)bounds->stride_b, (long long)bounds->stride_t};
+               (double *)factor, info, dt, d->nbatch, d->T, keep, (long long)bounds->stride_b, (long long)bounds->stride_t,
+               xbounds ? xbounds->lower : nullptr, xbounds ? xbounds->upper : nullptr,
+               xbounds ? (long long)xbounds->stride_b : 0, xbounds ? (long long)xbounds->stride_t : 0};
     return visit<int>(dyn_id, DQP_ERR_BAD_ARG, [&](auto model) {
         return run_newton_layout<typename decltype(model)::Map>(P, stream);
     });
@@ -173,6 +180,19 @@ dqp_al_banded_newton_step_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt
 {
     return dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, update, factor, info,
                                                   stream, 1);
+}
+
+// The step with a state box (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per problem
+__attribute__((visibility("default"))) int
+dqp_al_banded_newton_step_xbounds(const dqp_al_mpc_dims *d, int model, double dt, const double *xu, const double *x0,
+                                  const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                  const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *update, void *factor,
+                                  int32_t *info, void *stream)
+{
+    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
+    if (rc) return rc;
+    return dqp::al_banded_newton_step_keep_bounds(d, model, dt, xu, x0, Qdiag, q, lam, rho, bounds, update, factor, info,
+                                                  stream, 1, xbounds);
 }
 
 __attribute__((visibility("default"))) int

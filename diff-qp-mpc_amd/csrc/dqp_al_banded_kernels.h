@@ -65,6 +65,8 @@ struct BandP {
                         // factor on chip (LF below) then leave `fac` untouched; 1: write it
     long long bsb, bst; // bound layout (dqp_al_bounds.h): ul / uu of (b, t, k) at [b bsb + t bst + k]; read by the
                         // StridedBounds<> instantiations only, (0, 0) launches the vector ones
+    const double *xlo, *xhi;    // state box (BoxBounds<> instantiations only, else NULL): lower / upper of (b, t, k) at
+    long long xsb, xst;         // [b xsb + t xst + k]; lam then has 2 T nx more rows per problem, behind the control rows
 };
 
 }  // namespace dqp
@@ -77,6 +79,8 @@ using namespace dqp::r16;
 using dqp::BandP;
 using dqp::StridedBounds;
 using dqp::strided_bounds;
+using dqp::BoxBounds;
+using dqp::box_bounds;
 using dqp::dyn::Dual;
 
 // Phase clock of the instrumented build (tools/stamps_band.py; compiled out otherwise).  Each stamp drains the memory
@@ -107,6 +111,7 @@ template <int NX_, int NU_> struct Given { static constexpr int NX = NX_, NU = N
 template <class M> struct is_given { static constexpr bool value = false; };
 template <int A, int B_> struct is_given<Given<A, B_>> { static constexpr bool value = true; };
 template <class M> struct is_given<StridedBounds<M>> : is_given<M> {};
+template <class M> struct is_given<dqp::BoxBounds<M>> : is_given<M> {};
 
 template <class Map> struct BandCfg {
     static constexpr int NX = Map::NX, NU = Map::NU, NT = NX + NU;
@@ -272,7 +277,10 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
     if (!live) b = P.B - 1;
     const int T = P.T, neq = T * NX;
     const double *xu = P.xu + b * (long long)T * NT, *Qd = P.Qd + b * (long long)T * NT, *q = P.q + b * (long long)T * NT;
-    const double *lam = P.lam + b * (long long)(neq + 2 * T * NU), *x0 = P.x0 + b * NX;
+    // state box (BoxBounds<>): 2 T nx more rows per problem behind the control rows, per knot [x - upper, lower - x]
+    constexpr bool XB = box_bounds<Map>::value;
+    [[maybe_unused]] const int nxrow = XB ? neq + 2 * T * NU : 0;        // the first state row
+    const double *lam = P.lam + b * (long long)(neq + 2 * T * NU + (XB ? 2 * T * NX : 0)), *x0 = P.x0 + b * NX;
     const double rho = P.rho[b];
     double *fac = P.fac + b * (long long)T * NT * C::ROW;
     const bool inT = r < NT;
@@ -280,6 +288,8 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
     constexpr bool SB = strided_bounds<Map>::value;
     const double *ulb = P.ul, *uub = P.uu;
     if constexpr (SB) { ulb += b * P.bsb; uub += b * P.bsb; }
+    const double *xlb = nullptr, *xhb = nullptr;
+    if constexpr (XB) { xlb = P.xlo + b * P.xsb; xhb = P.xhi + b * P.xsb; }
 
     double Mprev[NX], yprev[1] = {0.0}, mu_prev[NX];
     int bad = 0;
@@ -373,9 +383,18 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
                 else { uut = P.uu[i]; ult = P.ul[i]; }
                 const double rup = zr - uut, rlo = ult - zr;
                 const double lup = lam[row], llo = lam[row + NU];
+                [[maybe_unused]] double xup = 0.0, xlw = 0.0, lxu = 0.0, lxl = 0.0;
+                if constexpr (XB) {     // the knot's state pair and its two multipliers: one coalesced load each
+                    xup = zr - xhb[t * P.xst + rx]; xlw = xlb[t * P.xst + rx] - zr;
+                    lxu = lam[nxrow + t * 2 * NX + rx]; lxl = lam[nxrow + t * 2 * NX + NX + rx];
+                }
                 if (r < NX) {
                     g += (t > 0) ? prev : first;
                     dg += rho;
+                    if constexpr (XB) {
+                        g += (lxu + rho * fmax(xup, 0.0)) - (lxl + rho * fmax(xlw, 0.0));
+                        dg += rho * ((xup > 0.0 ? 1.0 : 0.0) + (xlw > 0.0 ? 1.0 : 0.0));
+                    }
                 } else if (inT) {
                     g += (lup + rho * fmax(rup, 0.0)) - (llo + rho * fmax(rlo, 0.0));
                     dg += rho * ((rup > 0.0 ? 1.0 : 0.0) + (rlo > 0.0 ? 1.0 : 0.0));
@@ -477,6 +496,7 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
             for (int j = 0; j < NX; ++j) pxnk[j] = xu[tn * NT + j];
         };
         double pz[NT], pxn1[NX], plam[NX], pfx[NX], pcol[NX], pzr, pqd, pq, plu, pll, puu = 0.0, pul = 0.0;
+        [[maybe_unused]] double pxh = 0.0, pxl = 0.0, plxu = 0.0, plxl = 0.0;
         auto load_knot = [&](int t) {
             const bool dynrow = t < T - 1;
             if constexpr (!KB) {
@@ -503,6 +523,10 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
             const int row = neq + t * 2 * NU + iu;
             plu = lam[row]; pll = lam[row + NU];
             if constexpr (SB) { puu = uub[t * P.bst + iu]; pul = ulb[t * P.bst + iu]; }
+            if constexpr (XB) {     // the knot's state pair and its two multipliers, with the knot's other per-lane loads
+                pxh = xhb[t * P.xst + rx]; pxl = xlb[t * P.xst + rx];
+                plxu = lam[nxrow + t * 2 * NX + rx]; plxl = lam[nxrow + t * 2 * NX + NX + rx];
+            }
         };
         double sH[NT], sM[NX], srd = 0.0, sy = 0.0;              // knot t - 1's factor rows, stored during knot t
         auto store_knot = [&](int t, const double (&Hrow)[NT], double rdv, const double (&Mrow)[NX], double yv) {
@@ -534,6 +558,8 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
             for (int j = 0; j < NX; ++j) { lamt[j] = plam[j]; fxv[j] = pfx[j]; colv[j] = pcol[j]; }
             const double zr = pzr, qdr = pqd, qr = pq, lup = plu, llo = pll;
             const double uut = SB ? puu : uur, ult = SB ? pul : ulr;
+            [[maybe_unused]] double xup = 0.0, xlw = 0.0, lxu = 0.0, lxl = 0.0;
+            if constexpr (XB) { xup = zr - pxh; xlw = pxl - zr; lxu = plxu; lxl = plxl; }
             const bool dynrow = t < T - 1;
             if (t + 1 < T) load_knot(t + 1);
             if constexpr (!LF) { if (t > 0) store_knot(t - 1, sH, srd, sM, sy); }
@@ -600,6 +626,10 @@ __global__ __launch_bounds__(64) void al_banded_newton_kernel(BandP P BAND_STAMP
                 if (r < NX) {
                     g += (t > 0) ? prev : first;
                     dg += rho;
+                    if constexpr (XB) {
+                        g += (lxu + rho * fmax(xup, 0.0)) - (lxl + rho * fmax(xlw, 0.0));
+                        dg += rho * ((xup > 0.0 ? 1.0 : 0.0) + (xlw > 0.0 ? 1.0 : 0.0));
+                    }
                 } else if (inT) {
                     g += (lup + rho * fmax(rup, 0.0)) - (llo + rho * fmax(rlo, 0.0));
                     dg += rho * ((rup > 0.0 ? 1.0 : 0.0) + (rlo > 0.0 ? 1.0 : 0.0));

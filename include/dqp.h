@@ -34,7 +34,10 @@ extern "C" {
                            dqp_mpc_linearize, dqp_mpc_sqp_supported / _workspace_bytes / _rounds -- the SQP rounds of
                            qp_wrapper.MPC for a registered model, enqueued by one call;
                            dqp_deq_supported / _partial_bytes / _ln_forward / _ln_backward / _res_forward / _res_backward --
-                           the LayerNorm stages of the DEQ-MPC network as fused fp32 kernels;)
+                           the LayerNorm stages of the DEQ-MPC network as fused fp32 kernels;
+                           dqp_al_ncon_xbounds, dqp_al_banded_newton_step_xbounds, dqp_al_newton_solve_xbounds (+ _bytes),
+                           dqp_al_outer_update_xbounds, dqp_al_mpc_solve_xbounds (+ _bytes) -- state bounds on the
+                           block-tridiagonal AL paths;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -672,6 +675,54 @@ int dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *dims, const doub
                                          const double *Qdiag, const double *q, const double *lam, const double *rho,
                                          const dqp_al_bounds *bounds, const double *x_next, const double *Jx,
                                          const double *Ju, double *update, void *factor, int32_t *info, void *stream);
+
+/*
+ * State bounds x_lower <= x_t <= x_upper on the block-tridiagonal AL paths of a registered model (additive at 303).
+ * Each `_xbounds` entry below is its `_bounds` twin plus one `const dqp_al_bounds *xbounds` behind `bounds`, every other
+ * argument unchanged (dqp_al_newton_solve_xbounds is the block-tridiagonal form only and has no `banded`).  The state box
+ * is a second dqp_al_bounds with n_state in place of n_ctrl in the stride rules above: lower / upper of sample b, knot t,
+ * state k at [b * stride_b + t * stride_t + k], layouts (0, 0), (0, n_state), (n_state, 0), (T n_state, 0),
+ * (T n_state, n_state).  Bounds must be finite (a row of an infinite bound would make 0 * inf in lam . res): use a large
+ * finite number for "no bound".
+ *
+ * Rows: res = [ equality rows (T n) | control rows (2 T m) | state rows (2 T n) ], the first two blocks where they were;
+ * the state block is knot-major, per knot [x_t - x_upper (n), x_lower - x_t (n)], all knots 0 .. T-1 (knot 0's rows are
+ * constant along a line search: x_0 is pinned to x0), clamped at 0 for the penalty term and their multipliers clamped at
+ * 0 by the outer update, like the control rows.  lam, lam_new, lam_in, prev_lam and hist_lam have
+ * dqp_al_ncon_xbounds(dims) = T n + 2 T m + 2 T n columns.  A state row adds to the diagonal of H_tt and to the gradient
+ * of its knot only, so the factor keeps its shape: dqp_al_banded_factor_bytes and dqp_al_banded_solve (the backward) serve
+ * these entries as they are.  The `_bytes` queries are those of the twins.
+ *
+ * Return codes, in front of the nbatch == 0 return and in this order: DQP_ERR_BAD_ARG for a null dims, nbatch < 0,
+ * n_state / n_ctrl <= 0, T < 2, a null `bounds` / `xbounds` or one with strides outside its table;
+ * DQP_ERR_TOO_LARGE for n_state + n_ctrl > 16 or n_state > 12; DQP_ERR_BAD_ARG for a `model` that is not registered or
+ * whose sizes are not the dims'.  Then nbatch == 0 is DQP_OK with nothing enqueued; behind it null buffers (the lower /
+ * upper of either box included) and the twins' other argument errors are DQP_ERR_BAD_ARG.  Kernels: the BoxBounds<>
+ * instantiations of the Newton, line-search and outer-update kernels (csrc/dqp_al_bounds.h), which read both boxes
+ * through their strides.  Only enqueue on `stream`.
+ */
+int32_t dqp_al_ncon_xbounds(const dqp_al_mpc_dims *dims);
+int dqp_al_banded_newton_step_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, const double *xu,
+                                      const double *x0, const double *Qdiag, const double *q, const double *lam,
+                                      const double *rho, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds,
+                                      double *update, void *factor, int32_t *info, void *stream);
+size_t dqp_al_newton_solve_xbounds_bytes(const dqp_al_mpc_dims *dims);
+int dqp_al_newton_solve_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, int32_t n_steps, const double *x0,
+                                const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *xu, double *L,
+                                double *status, int32_t *fail, void *workspace, void *stream);
+int dqp_al_outer_update_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, const double *xu, const double *x0,
+                                const double *lam, const double *rho, const double *Qdiag, const double *q,
+                                const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *lam_new, double *cost,
+                                double *res_norm, void *stream);
+size_t dqp_al_mpc_solve_xbounds_bytes(const dqp_al_mpc_dims *dims);
+int dqp_al_mpc_solve_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, int32_t al_iter, int32_t newton_steps,
+                             const double *x_init, const double *u_init, const double *x0, const double *Qdiag,
+                             const double *q, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds,
+                             const double *lam_in, const double *rho_in, const double *prev_cost, const double *prev_lam,
+                             const double *prev_rho, int32_t n_prev, double *xu, double *hist_cost, double *hist_lam,
+                             double *hist_rho, double *res_norm, double *factor, double *status, int32_t *fail,
+                             void *workspace, void *stream);
 
 /*
  * Per-sample, per-knot control bounds of the MPC QP (additive at 303).  dqp_mpc_assemble, dqp_mpc_qp_forward and
