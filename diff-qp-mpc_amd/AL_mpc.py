@@ -14,9 +14,12 @@ State bounds (`x_lower` / `x_upper`, both or neither; finite; (n,), (T, n), (B, 
 [x_t - x_upper, x_lower - x_t] of every knot, appended behind the control rows -- the multipliers then have
 T n + 2 T m + 2 T n columns.  A registered device model (n_state + n_ctrl <= 16, n_state <= 12, fp64) runs them on the
 block-tridiagonal kernels (dqp_al_mpc_solve_xbounds, or per AL iteration dqp_al_newton_solve_xbounds +
-dqp_al_outer_update_xbounds; the backward is the one without them).  Everything else takes the general torch path with
-the state rows: the single-launch solve (PERSISTENT_SOLVE), caller-linearised dynamics (NewtonALBandedJac), the dense
-AL kernel route, and the LU fallback after a Cholesky failure.
+dqp_al_outer_update_xbounds; the backward is the one without them).  A caller's own dynamics module (dx, dx_jac) runs
+them on the caller-linearised block-tridiagonal step at every compiled pair, the wide ones included
+(NewtonALBandedJac: dqp_al_banded_newton_step_jac_xbounds, the line search's merit by dqp_al_merit_xbounds; the outer
+update stays in torch, which needs the module anyway).  Everything else takes the general torch path with the state
+rows: the single-launch solve (PERSISTENT_SOLVE), the dense AL kernel route, and the LU fallback after a Cholesky
+failure.
 """
 import torch
 from torch.nn import Module
@@ -207,18 +210,21 @@ class MPC(Module):
                     lambda xi, Qi, qi: self.compute_cost(xi, Qi, qi),
                     lambda xi, Qi, qi, yi: self.merit_grad_hess(xi, Qi, qi, dx, dx_jac, x0, yi, rho_i),
                     xu, x0, lamda, rho, Qg, qg, 1e-3, 1e-6, True)
+            # (a registered model that was kept off its own device path -- FUSED_NEWTON_AL = False, fp32 -- takes the
+            # general path with a state box, as before)
             banded_jac = (not device_path and _fused and BANDED_USER_DYNAMICS and x.is_cuda and dx_jac is not None
-                          and self.x_lower is None
+                          and not (xb and isinstance(dx, DeviceDynamics))
                           and al_utils.bounds_supported(self.u_lower, self.u_upper, x.size(0), self.T, self.n_ctrl)
                           and self.T * nt > BANDED_USER_DYNAMICS_FROM_NZ
-                          and al_utils.banded_jac_supported(self.n_batch, self.n_state, self.n_ctrl, self.T, strided))
+                          and al_utils.banded_jac_supported(self.n_batch, self.n_state, self.n_ctrl, self.T, strided,
+                                                            state_bounds=xb))
             if banded_jac:
                 # caller-supplied dynamics at a horizon the dense Newton step cannot hold (nz > 128): its own
                 # Jacobians into the block-tridiagonal step
                 out, status, failed = al_utils.NewtonALBandedJac.apply(
                     lambda xi, Qi, qi, yi, x0i=x0, rhoi=rho_i, grad=False:
                         self.merit_function(xi, Qi, qi, dx, x0i, yi, rhoi, grad),
-                    dx_jac, xu, x0, lamda, rho, Q, q, self.u_lower, self.u_upper, True)
+                    dx_jac, xu, x0, lamda, rho, Q, q, self.u_lower, self.u_upper, True, self.x_lower, self.x_upper)
                 fail_flags.append(failed.reshape(1).to(torch.int32))
             elif device_path and torch.is_tensor(rho):
                 # registered device model: the four Newton steps in one C-ABI call (dqp_al_newton_solve);

@@ -46,7 +46,7 @@ RIC_HOST_PARTS = [
 RIC_PARTS = [("native", RIC_SIZES), ("wide", RICW_SIZES)] + [("host%d" % k, p) for k, p in enumerate(RIC_HOST_PARTS)]
 
 PLAIN_SOURCES = ["dqp_pdipm.hip", "dqp_mpc.hip", "dqp_mpc_qp.hip", "dqp_al.hip", "dqp_term.hip", "dqp_dyn.hip",
-                 "dqp_al_banded.hip", "dqp_al_banded_wide.hip", "dqp_trace.hip", "dqp_big.hip", "dqp_shared_grad.hip",
+                 "dqp_al_banded.hip", "dqp_al_banded_wide.hip", "dqp_al_banded_box.hip", "dqp_trace.hip", "dqp_big.hip", "dqp_shared_grad.hip",
                  "dqp_al_fused.hip", "dqp_mpc_sqp.hip", "dqp_deq.hip"]
 SOURCES = PLAIN_SOURCES + ["dqp_r16.hip", "dqp_r16n.hip", "dqp_dispatch.hip", "dqp_ric.hip", "dqp_ric_pad.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-MD",
@@ -89,6 +89,9 @@ def _jobs():
     for src in PLAIN_SOURCES:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         jobs.append((obj, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]))
+    # the wide NewtonAL pairs with a state box: the same source once more, an object of its own next to the first
+    obj = os.path.join(CSRC, "dqp_al_banded_widebox.o")
+    jobs.append((obj, [cc] + FLAGS + ["-DDQP_BAND_WIDE_BOX", "-c", os.path.join(CSRC, "dqp_al_banded_wide.hip"), "-o", obj]))
     xs = lambda pairs: " ".join("X(%d,%d)" % p for p in pairs)
     host = [p for part in RIC_HOST_PARTS for p in part]
     # Cfg::INT_LDS of csrc/dqp_ric_kernels.h reads the 16-lane host pairs: the same list in every object
@@ -111,7 +114,7 @@ def _jobs():
         if m is None:
             if "ric" in name and "pad" not in name:            # stage-wise kernels: ~2 min (dqp_ric_native), ~30-50 s the others
                 return 10 ** 5
-            if "banded_wide" in name:                          # three wide pairs in one object: ~6 min
+            if "banded_wide" in name:                          # three wide pairs in one object (two of them): ~6 min
                 return 10 ** 9
             return 10 ** 9 if "pdipm" in name else 1          # the generic kernels: ~2 min
         n, mm, e = m

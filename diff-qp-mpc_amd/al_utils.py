@@ -284,13 +284,14 @@ def compute_cost_gradient(xu, Q, q, diag_cost=True):
 
 def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_upper, diag_cost=True):
     """cost + rho/2 |res_clamp|^2 + lamda . res; a leading candidate axis (n_ls,B,T,nt) is
-    folded into the batch (al_utils.py:37-59).  With state bounds the torch ops below run (dqp_al_merit has the fixed
-    row order without state rows)."""
+    folded into the batch (al_utils.py:37-59).  On the device without autograd it is one launch: dqp_al_merit_bounds, or
+    with state bounds dqp_al_merit_xbounds (the state rows behind the control rows); otherwise the torch ops below."""
     m_ctrl = xu.shape[-1] - x0.shape[-1]
-    if (xu.is_cuda and not torch.is_grad_enabled() and x_lower is None and x_upper is None
+    if (xu.is_cuda and not torch.is_grad_enabled()
             and bounds_supported(u_lower, u_upper, x0.shape[0], xu.shape[-2], m_ctrl)    # a layout the kernel takes
-            and (u_lower.dim() == 1 or bounds_strided(u_lower, m_ctrl))):
-        return _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper)
+            and (u_lower.dim() == 1 or bounds_strided(u_lower, m_ctrl))
+            and (x_lower is None or bounds_supported(x_lower, x_upper, x0.shape[0], xu.shape[-2], x0.shape[-1]))):
+        return _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper, x_lower, x_upper)
     if xu.dim() == 4:
         k, B = xu.shape[:2]
         rep = lambda t: t[None].expand(k, *t.shape).reshape(k * B, *t.shape[1:])
@@ -308,9 +309,9 @@ def merit_function(xu, Q, q, dx, x0, lamda, rho, x_lower, x_upper, u_lower, u_up
     return compute_cost(xu, Q, q) + 0.5 * rho[:, 0] * (resc * resc).sum(1) + (lamda * res).sum(1)
 
 
-def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper):
-    """merit_function through dqp_al_merit: the dynamics are evaluated by the caller's module (one
-    batched call over all candidates), cost + penalty + multiplier terms in one launch."""
+def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper, x_lower=None, x_upper=None):
+    """merit_function through dqp_al_merit_bounds / dqp_al_merit_xbounds: the dynamics are evaluated by the caller's
+    module (one batched call over all candidates), cost + penalty + multiplier terms in one launch."""
     k = xu.shape[0] if xu.dim() == 4 else 1
     flat = xu.reshape(-1, *xu.shape[-2:])
     n = x0.shape[-1]
@@ -326,7 +327,11 @@ def _merit_fused(xu, Q, q, dx, x0, lamda, rho, u_lower, u_upper):
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
     keep = [d64(x0), d64(Q), d64(q), d64(lamda), d64(rho).reshape(B)]
     bd = bounds_layout(u_lower, u_upper, B, T, m)
-    _lib.call("dqp_al_merit_bounds", xu.device, dims, k, xu64, xn64, *keep, bd.ref(), merit)
+    if x_lower is not None:
+        xbd = bounds_layout(x_lower, x_upper, B, T, n)
+        _lib.call("dqp_al_merit_xbounds", xu.device, dims, k, xu64, xn64, *keep, bd.ref(), xbd.ref(), merit)
+    else:
+        _lib.call("dqp_al_merit_bounds", xu.device, dims, k, xu64, xn64, *keep, bd.ref(), merit)
     return merit.to(xu.dtype)
 
 
@@ -498,13 +503,14 @@ def _banded_solve(dims, dyn_id, factor, x_grad):
     return g
 
 
-def banded_jac_supported(B, n, m, T, strided=False):
+def banded_jac_supported(B, n, m, T, strided=False, state_bounds=False):
     """A block-tridiagonal Newton step exists for caller-linearised dynamics of these sizes (n + m <= 16: 8- / 16-lane
     kernels; the wide pairs up to n + m = 32: one problem per half-wavefront).  `strided`: with per-sample / per-knot
-    bounds, which the wide pairs do not take."""
+    bounds, which the wide pairs take only next to a state box (`state_bounds`: that kernel reads both boxes through
+    strides)."""
     dims = _lib.dqp_al_mpc_dims(B, n, m, T)
     lib = _lib.load()
-    if strided:         # dqp_al_banded_factor_bytes(dims, 0) is 0 at the wide pairs
+    if strided and not state_bounds:         # dqp_al_banded_factor_bytes(dims, 0) is 0 at the wide pairs
         return int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), 0)) > 0
     return int(lib.dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) > 0
 
@@ -514,10 +520,11 @@ class NewtonALBandedJac(torch.autograd.Function):
     linearisation (x_next, (Jx, Ju)) = dx_jac(x, u) goes to dqp_al_banded_newton_step_jac -- gradient,
     block-tridiagonal Hessian, block Cholesky and solve in one launch, no (B, ncon, nz) Jacobian and no
     (B, nz, nz) Hessian in memory (the dense step stops at nz = 128) -- and the line search evaluates the
-    module on the 20 candidates as NewtonAL does."""
+    module on the 20 candidates as NewtonAL does.  `x_lower` / `x_upper`: a state box
+    (dqp_al_banded_newton_step_jac_xbounds; `lam` then has the state rows' columns)."""
 
     @staticmethod
-    def forward(ctx, meritfn, dx_jac, xi, x0, lam, rho, Q, q, u_lower, u_upper, ls):
+    def forward(ctx, meritfn, dx_jac, xi, x0, lam, rho, Q, q, u_lower, u_upper, ls, x_lower=None, x_upper=None):
         lib = _lib.load()
         B, T, nt = xi.shape
         n = x0.shape[-1]
@@ -529,6 +536,7 @@ class NewtonALBandedJac(torch.autograd.Function):
         rho_t = rho if torch.is_tensor(rho) else torch.full((B,), float(rho), **kw)
         keep = [d64(x0), d64(Q), d64(q), d64(lam), d64(rho_t).reshape(B)]
         bd = bounds_layout(u_lower, u_upper, B, T, m)
+        xbd = bounds_layout(x_lower, x_upper, B, T, n) if x_lower is not None else None
         fac = torch.empty(int(lib.dqp_al_banded_jac_factor_bytes(ctypes.byref(dims))) // 8, **kw)
         upd = torch.empty(B, T, nt, **kw)
         info = torch.empty(B, dtype=torch.int32, device=dev)
@@ -542,8 +550,12 @@ class NewtonALBandedJac(torch.autograd.Function):
                 xs = xu[:, :-1, :n].reshape(-1, n).to(xi.dtype).requires_grad_(True)
                 us = xu[:, :-1, n:].reshape(-1, m).to(xi.dtype).requires_grad_(True)
                 x_next, (Jx, Ju) = dx_jac(xs, us)
-            _lib.call("dqp_al_banded_newton_step_jac_bounds", dev, dims, xu, *keep, bd.ref(), d64(x_next), d64(Jx), d64(Ju),
-                      upd, fac, info)
+            if xbd is not None:
+                _lib.call("dqp_al_banded_newton_step_jac_xbounds", dev, dims, xu, *keep, bd.ref(), xbd.ref(), d64(x_next),
+                          d64(Jx), d64(Ju), upd, fac, info)
+            else:
+                _lib.call("dqp_al_banded_newton_step_jac_bounds", dev, dims, xu, *keep, bd.ref(), d64(x_next), d64(Jx),
+                          d64(Ju), upd, fac, info)
             if bool((info != 0).any()):     # a pivot was not positive: the reference switches to an LU solve
                 failed = True               # (al_utils.py:419-427); here the caller re-runs the dense path
                 break
@@ -565,7 +577,7 @@ class NewtonALBandedJac(torch.autograd.Function):
         fac, x = ctx.saved_tensors
         g = _banded_solve(ctx.dims, 0, fac, x_grad).to(x_grad.dtype)
         # diagonal cost: dQ = g * x, dq = g                          al_utils.py:482-485
-        return (None,) * 6 + (g * x, g, None, None, None)
+        return (None,) * 6 + (g * x, g, None, None, None, None, None)
 
 
 class NewtonALDevice(torch.autograd.Function):

@@ -510,6 +510,9 @@ struct MeritP {
 // struct, so that not even the offsets of their hidden kernel arguments move.
 struct MeritPS : MeritP { long long bsb, bst; };
 template <bool SB> using MeritArg = std::conditional_t<SB, MeritPS, MeritP>;
+// the argument of the kernel with state rows (dqp_al_merit_xbounds): + the state box, lower / upper of (b, t, j) at
+// [b xsb + t xst + j].  It grows at its end, so the two kernels above keep theirs.
+struct MeritPX : MeritPS { const double *xlo, *xhi; long long xsb, xst; };
 
 // SB: per-sample / per-knot bounds at [b bsb + t bst + i]; !SB: the n_ctrl-vector
 template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritArg<SB> P)
@@ -542,6 +545,52 @@ template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritA
             const double u = z[n + i], up = u - uut, lo = ult - u;
             const int row = neq + t * 2 * m + i;
             acc += lam[row] * up + lam[row + m] * lo + 0.5 * rho * (fmax(up, 0.0) * fmax(up, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
+        }
+    }
+    acc = dqp::r16::row_sum(acc);
+    if (r == 0 && item < total) P.merit[item] = acc;
+}
+
+// The third instantiation: the same sweep with the state rows of dqp_al_bounds.h behind the control rows -- per knot
+// [x - x_upper (n), x_lower - x (n)], knot 0's included -- and both boxes read through their strides.  An overload on a
+// second template parameter with a body of its own: the two kernels above keep their names in a trace and their
+// instruction streams (sharing the body through a helper moved three of their instructions).
+template <bool SB, bool XB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritPX P)
+{
+    static_assert(SB && XB, "with a state box both boxes are read through their strides");
+    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, nxrow = neq + 2 * T * m, ncon = nxrow + 2 * T * n;
+    const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // (cand, problem)
+    const int r = threadIdx.x & 15;
+    const long long total = (long long)P.ncand * P.B;
+    const long long it = item < total ? item : total - 1;
+    const long long b = it % P.B;
+    const double *xu = P.xu + it * (long long)T * nt, *xn = P.xn + it * (long long)(T - 1) * n;
+    const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
+    const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
+    const double *ul = P.ul + b * P.bsb, *uu = P.uu + b * P.bsb, *xlo = P.xlo + b * P.xsb, *xhi = P.xhi + b * P.xsb;
+    const double rho = P.rho[b];
+    auto row_pair = [&](double v, double upper, double lower, double lam_up, double lam_lo) {
+        const double up = v - upper, lo = lower - v;
+        return lam_up * up + lam_lo * lo + 0.5 * rho * (fmax(up, 0.0) * fmax(up, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
+    };
+    double acc = 0.0;
+    for (int t = r; t < T; t += 16) {
+        const double *z = xu + t * nt;
+        for (int j = 0; j < nt; ++j) acc += (0.5 * Qd[t * nt + j] * z[j] + q[t * nt + j]) * z[j];
+        for (int j = 0; j < n; ++j) {                       // equality row block of knot t
+            double res;
+            int row;
+            if (t < T - 1) { res = xu[(t + 1) * nt + j] - xn[t * n + j]; row = t * n + j; }
+            else { res = xu[j] - x0[j]; row = (T - 1) * n + j; }
+            acc += (0.5 * rho * res + lam[row]) * res;
+        }
+        for (int i = 0; i < m; ++i) {                       // control rows of knot t
+            const int row = neq + t * 2 * m + i;
+            acc += row_pair(z[n + i], uu[t * P.bst + i], ul[t * P.bst + i], lam[row], lam[row + m]);
+        }
+        for (int j = 0; j < n; ++j) {                       // state rows of knot t
+            const int row = nxrow + t * 2 * n + j;
+            acc += row_pair(z[j], xhi[t * P.xst + j], xlo[t * P.xst + j], lam[row], lam[row + n]);
         }
     }
     acc = dqp::r16::row_sum(acc);
@@ -1273,6 +1322,28 @@ dqp_al_merit_bounds(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, c
     else
         DQP_LAUNCH(al_merit_kernel<false>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
                    static_cast<const MeritP &>(P));
+    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+}
+
+// The merit with state rows (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per problem; any (n_state, n_ctrl)
+__attribute__((visibility("default"))) int
+dqp_al_merit_xbounds(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, const double *x_next,
+                     const double *x0, const double *Qdiag, const double *q, const double *lam,
+                     const double *rho, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *merit,
+                     void *stream)
+{
+    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || ncand < 0) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK || dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK)
+        return DQP_ERR_BAD_ARG;
+    if (d->nbatch == 0 || ncand == 0) return DQP_OK;
+    if (!xu || !x_next || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !xbounds->lower ||
+        !xbounds->upper || !merit)
+        return DQP_ERR_BAD_ARG;
+    MeritPX P = {{{xu, x_next, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, merit, d->nbatch, d->n_state,
+                   d->n_ctrl, d->T, ncand}, (long long)bounds->stride_b, (long long)bounds->stride_t},
+                 xbounds->lower, xbounds->upper, (long long)xbounds->stride_b, (long long)xbounds->stride_t};
+    const long long total = (long long)ncand * d->nbatch;
+    DQP_LAUNCH((al_merit_kernel<true, true>), dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream, P);
     return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 

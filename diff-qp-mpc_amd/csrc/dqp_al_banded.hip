@@ -1,7 +1,8 @@
 // dqp_al_banded.hip -- host side of the block-tridiagonal NewtonAL kernels (dqp_al_banded_kernels.h) at knots of up to 16
-// variables: the choice of the lane group and of the LDS-resident factor, the launches for registered models and for
-// the caller-linearised pairs of DQP_BAND_SIZES, and the C entry points (include/dqp.h).  The DQP_BAND_WIDE_SIZES pairs
-// are launched by dqp_al_banded_wide.hip.
+// variables: the choice of the lane group (the launch rule itself: dqp_al_banded_launch.h), the launches for registered
+// models and for the caller-linearised pairs of DQP_BAND_SIZES, and the C entry points (include/dqp.h).  The
+// DQP_BAND_WIDE_SIZES pairs are launched by dqp_al_banded_wide.hip, the DQP_BAND_SIZES pairs with a state box by
+// dqp_al_banded_box.hip.
 #include <stdlib.h>
 
 #include "dqp_al_banded_kernels.h"
@@ -28,11 +29,12 @@ unsigned long long *g_band_stamps = nullptr;
 #define BAND_STAMP_ARG
 #endif
 
-// Eight problems per wavefront where a knot fits a half row AND the batch is more than one wavefront per SIMD at
-// four per wavefront (these kernels hold one wavefront per SIMD): below that the launch is one latency chain per
-// wavefront either way and the narrower group only idles SIMDs (cartpole-1 at B = 4096: 2.0 ms both ways;
-// cartpole-2 at B = 8192: 2.24 -> 1.97 ms per AL_mpc.MPC call).
-template <class Map> constexpr bool half_row() { return Map::NX + Map::NU <= 8; }
+}  // namespace
+
+#include "dqp_al_banded_launch.h"
+
+namespace {
+
 // g_lane_group: 0 = by batch size, 8 / 16 = pinned (dqp_al_lane_group; initial value from DQP_AL_LANE_GROUP, read once)
 static int g_lane_group = -1;
 static int g_simds = 0;
@@ -51,27 +53,6 @@ inline bool narrow(int B)
         g_simds = 4 * cus;
     }
     return (B + 3) / 4 > g_simds;
-}
-template <class Map> int run_newton(const BandP &P, void *stream)
-{
-    if constexpr (half_row<Map>()) {
-        if (narrow(P.B)) {
-            if constexpr (Map::NX + Map::NU >= 6) {
-                // the one-wavefront-per-SIMD half-row models: the factor stays in LDS where the horizon allows (four
-                // workgroups per CU next to their 5 KB tiles)
-                using C = BandCfg<Map>;
-                const size_t bytes = (size_t)P.T * (C::ROW + 1) * 8 * C::NT * sizeof(double);
-                if (bytes <= 34 * 1024) {
-                    DQP_LAUNCH((al_banded_newton_kernel<Map, 8, true>), dim3((P.B + 7) / 8), dim3(64), bytes, (hipStream_t)stream, P BAND_STAMP_ARG);
-                    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-                }
-            }
-            DQP_LAUNCH((al_banded_newton_kernel<Map, 8>), dim3((P.B + 7) / 8), dim3(64), 0, (hipStream_t)stream, P BAND_STAMP_ARG);
-            return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-        }
-    }
-    DQP_LAUNCH((al_banded_newton_kernel<Map, 16>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P BAND_STAMP_ARG);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
 }
 // the vector instantiation at (0, 0), the strided one otherwise; with a state box the BoxBounds<> one (both boxes strided)
 template <class Map> int run_newton_layout(const BandP &P, void *stream)
@@ -110,6 +91,8 @@ int knot_doubles(int id, int n_, int m_)          // nt rows x (L row, 1/diag, M
 }  // namespace
 
 using namespace dqp::dyn;
+
+bool dqp::al_banded_narrow(int B) { return narrow(B); }
 
 extern "C" {
 
@@ -240,6 +223,30 @@ dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *d, const double *xu,
         return run_newton_layout<decltype(given)>(P, stream);
     });
     return rc == NOT_NARROW ? dqp::al_banded_wide_newton(d->n_state, d->n_ctrl, P, stream) : rc;
+}
+
+// The step for caller-linearised dynamics with a state box (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per
+// problem; BoxBounds<Given<n, m>> reads both boxes through their strides, at the wide pairs too
+__attribute__((visibility("default"))) int
+dqp_al_banded_newton_step_jac_xbounds(const dqp_al_mpc_dims *d, const double *xu, const double *x0, const double *Qdiag,
+                                      const double *q, const double *lam, const double *rho, const dqp_al_bounds *bounds,
+                                      const dqp_al_bounds *xbounds, const double *x_next, const double *Jx,
+                                      const double *Ju, double *update, void *factor, int32_t *info, void *stream)
+{
+    if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
+    if (dqp::al_bounds_layout(bounds, d) != DQP_OK || dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK)
+        return DQP_ERR_BAD_ARG;
+    const bool wide = given_wide(d->n_state, d->n_ctrl);
+    if (!wide && !given_supported(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
+    if (d->nbatch == 0) return DQP_OK;
+    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !xbounds->lower ||
+        !xbounds->upper || !x_next || !Jx || !Ju || !update || !factor)
+        return DQP_ERR_BAD_ARG;
+    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, x_next, Jx, Ju, update, (double *)factor,
+               info, 0.0, d->nbatch, d->T, 1, (long long)bounds->stride_b, (long long)bounds->stride_t,
+               xbounds->lower, xbounds->upper, (long long)xbounds->stride_b, (long long)xbounds->stride_t};
+    return wide ? dqp::al_banded_wide_box_newton(d->n_state, d->n_ctrl, P, stream)
+                : dqp::al_banded_box_newton(d->n_state, d->n_ctrl, P, stream);
 }
 
 __attribute__((visibility("default"))) int

@@ -9,7 +9,23 @@
 // keeps its form: per (b, t) nt rows x (nt + 1 + n) doubles, element-major over the knot's lanes
 // (dqp_al_banded_jac_factor_bytes).  No prefetch-ahead, half-row or LDS-factor variants, and no registered model is
 // this wide.
+//
+// Compiled twice (_build.py), the objects side by side: as it is -- the vector-bound Newton kernels and the solve
+// kernels -- and with -DDQP_BAND_WIDE_BOX: the Newton kernels with a state box, BoxBounds<Given<n, m>>, which read the
+// control bounds through their strides too (dqp_al_banded_newton_step_jac_xbounds).
 #include "dqp_al_banded_kernels.h"
+
+#ifdef DQP_BAND_WIDE_BOX
+
+int dqp::al_banded_wide_box_newton(int n, int m, const BandP &P, void *stream)
+{
+    return visit_pair<BAND_WIDE, int>(n, m, DQP_ERR_TOO_LARGE, [&](auto given) {
+        DQP_LAUNCH((al_banded_newton_kernel<BoxBounds<decltype(given)>, 32>), dim3((P.B + 1) / 2), dim3(64), 0, (hipStream_t)stream, P);
+        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    });
+}
+
+#else
 
 int dqp::al_banded_wide_newton(int n, int m, const BandP &P, void *stream)
 {
@@ -26,3 +42,5 @@ int dqp::al_banded_wide_solve(int n, int m, const BandP &P, void *stream)
         return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
     });
 }
+
+#endif

@@ -131,11 +131,14 @@ class DEQLayer(nn.Module):
 
 
 class Tracking_MPC(nn.Module):
-    """Tracks the network's reference with the differentiable MPC (policies.py:567-686)."""
+    """Tracks the network's reference with the differentiable MPC (policies.py:567-686).  `x_lower` / `x_upper`: a state
+    box for the augmented-Lagrangian solver (AL_mpc.MPC's shapes); the interior-point solver has no state rows."""
 
-    def __init__(self, args, env):
+    def __init__(self, args, env, x_lower=None, x_upper=None):
         super().__init__()
         self.args = args
+        if (x_lower is not None or x_upper is not None) and args.solver_type != "al":
+            raise ValueError("state bounds need solver_type 'al': the interior-point MPC has no state rows")
         self.nu, self.nx, self.nq, self.dt, self.T = env.nu, env.nx, getattr(env, "nq", args.nq), env.dt, args.T
         dyn, dyn_jac = env.dynamics, env.dynamics_derivatives
         if RECOGNISE_ENV_DYNAMICS and not isinstance(dyn, DeviceDynamics):
@@ -163,7 +166,8 @@ class Tracking_MPC(nn.Module):
         if args.solver_type == "al":
             self.ctrl = al_mpc.MPC(self.nx, self.nu, self.T, u_lower=self.u_lower, u_upper=self.u_upper,
                                    exit_unconverged=False, eps=1e-5, n_batch=self.bsz, backprop=False, verbose=0,
-                                   u_init=self.u_init, solver_type="dense", dtype=self.dtype)
+                                   u_init=self.u_init, solver_type="dense", dtype=self.dtype,
+                                   x_lower=x_lower, x_upper=x_upper)
         else:
             self.ctrl = ip_mpc.MPC(self.nx, self.nu, self.T, u_lower=self.u_lower.double(), u_upper=self.u_upper.double(),
                                    qp_iter=self.qp_iter, exit_unconverged=False, eps=1e-5, n_batch=self.bsz,

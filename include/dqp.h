@@ -37,7 +37,9 @@ extern "C" {
                            the LayerNorm stages of the DEQ-MPC network as fused fp32 kernels;
                            dqp_al_ncon_xbounds, dqp_al_banded_newton_step_xbounds, dqp_al_newton_solve_xbounds (+ _bytes),
                            dqp_al_outer_update_xbounds, dqp_al_mpc_solve_xbounds (+ _bytes) -- state bounds on the
-                           block-tridiagonal AL paths;)
+                           block-tridiagonal AL paths;
+                           dqp_al_banded_newton_step_jac_xbounds, dqp_al_merit_xbounds -- state bounds on the
+                           caller-linearised block-tridiagonal step and in the merit kernel;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -630,7 +632,9 @@ int dqp_al_lane_group(int width);
  *
  * Kernels: the block-tridiagonal Newton step (registered models and the DQP_BAND_SIZES pairs), the line-search / merit,
  * outer-update and single-launch kernels have a strided instantiation next to the vector one.  The DQP_BAND_WIDE_SIZES
- * pairs have none: dqp_al_banded_newton_step_jac_bounds returns DQP_ERR_TOO_LARGE for them at non-zero strides.
+ * pairs have none without a state box: dqp_al_banded_newton_step_jac_bounds returns DQP_ERR_TOO_LARGE for them at
+ * non-zero strides.  With a state box (dqp_al_banded_newton_step_jac_xbounds below) they take every layout of the table,
+ * because that kernel reads both boxes through their strides.
  * dqp_al_banded_solve (NewtonAL.backward) does not read the bounds -- the factor already carries the active set -- and
  * has no twin.  The single-launch solve stages the 2 T n_ctrl bounds of its problem in LDS next to the problem;
  * dqp_al_mpc_solve_fused_lds_bytes reports the launch's LDS (0 where _supported_bounds is 0).
@@ -677,7 +681,8 @@ int dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *dims, const doub
                                          const double *Ju, double *update, void *factor, int32_t *info, void *stream);
 
 /*
- * State bounds x_lower <= x_t <= x_upper on the block-tridiagonal AL paths of a registered model (additive at 303).
+ * State bounds x_lower <= x_t <= x_upper on the block-tridiagonal AL paths of a registered model (additive at 303; for
+ * caller-linearised dynamics see dqp_al_banded_newton_step_jac_xbounds below).
  * Each `_xbounds` entry below is its `_bounds` twin plus one `const dqp_al_bounds *xbounds` behind `bounds`, every other
  * argument unchanged (dqp_al_newton_solve_xbounds is the block-tridiagonal form only and has no `banded`).  The state box
  * is a second dqp_al_bounds with n_state in place of n_ctrl in the stride rules above: lower / upper of sample b, knot t,
@@ -723,6 +728,34 @@ int dqp_al_mpc_solve_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, 
                              const double *prev_rho, int32_t n_prev, double *xu, double *hist_cost, double *hist_lam,
                              double *hist_rho, double *res_norm, double *factor, double *status, int32_t *fail,
                              void *workspace, void *stream);
+
+/*
+ * State bounds for a dynamics the CALLER linearised (additive at 303): dqp_al_banded_newton_step_jac_bounds plus
+ * `xbounds` behind `bounds`, with the state box, the row order and lam's dqp_al_ncon_xbounds(dims) columns of the
+ * `_xbounds` entries above.  Kernels: al_banded_newton_kernel<BoxBounds<Given<n, m>>, G, LF> at every pair of
+ * DQP_BAND_SIZES (16 lanes; 8 where n_state + n_ctrl <= 8, by batch size or dqp_al_lane_group; the LDS-resident factor by
+ * the rule of the twin) and of DQP_BAND_WIDE_SIZES (32 lanes).  `bounds` takes every layout of its table at the wide
+ * pairs too.  `factor` has dqp_al_banded_jac_factor_bytes(dims) bytes and is applied by dqp_al_banded_solve(dims, 0, ...).
+ * Return codes, in this order: DQP_ERR_BAD_ARG for a null dims, nbatch < 0, n_state / n_ctrl < 1, T < 2, a null `bounds` /
+ * `xbounds` or one with strides outside its table; DQP_ERR_TOO_LARGE for a pair in neither list; DQP_OK with nothing
+ * enqueued for nbatch == 0; DQP_ERR_BAD_ARG for a null buffer, the lower / upper of either box included (`info` may be
+ * null).
+ *
+ * dqp_al_merit_xbounds: dqp_al_merit_bounds with the state rows -- the lane that sweeps knot t adds, for j < n_state,
+ * lam[row] up + lam[row + n] lo + rho / 2 (max(up, 0)^2 + max(lo, 0)^2), up = x - x_upper, lo = x_lower - x,
+ * row = T n + 2 T m + t 2 n + j, knot 0's rows included -- at any (n_state, n_ctrl): the sizes are run-time values of
+ * that kernel.  The checks of dqp_al_merit_bounds plus the state box's layout (in front of the nbatch == 0 / ncand == 0
+ * return) and its pointers (behind it).
+ */
+int dqp_al_banded_newton_step_jac_xbounds(const dqp_al_mpc_dims *dims, const double *xu, const double *x0,
+                                          const double *Qdiag, const double *q, const double *lam, const double *rho,
+                                          const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds,
+                                          const double *x_next, const double *Jx, const double *Ju, double *update,
+                                          void *factor, int32_t *info, void *stream);
+int dqp_al_merit_xbounds(const dqp_al_mpc_dims *dims, int32_t ncand, const double *xu, const double *x_next,
+                         const double *x0, const double *Qdiag, const double *q, const double *lam,
+                         const double *rho, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *merit,
+                         void *stream);
 
 /*
  * Per-sample, per-knot control bounds of the MPC QP (additive at 303).  dqp_mpc_assemble, dqp_mpc_qp_forward and
