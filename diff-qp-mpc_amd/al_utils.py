@@ -606,7 +606,7 @@ class NewtonALDevice(torch.autograd.Function):
             L = torch.empty(B, T * nt, T * nt, **kw)
         status = torch.empty(B, **kw)
         fail = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.dqp_al_newton_solve_bytes(ctypes.byref(dims), banded)) // 8 + 1, **kw)
+        ws = torch.empty(int(lib.dqp_al_newton_solve_bytes(ctypes.byref(dims), banded)) // 8, **kw)
         if x_lower is not None:     # state bounds: the block-tridiagonal form with the state rows (lam: ncon_x columns)
             assert banded, "state bounds run on the block-tridiagonal kernels only"
             xbd = bounds_layout(x_lower, x_upper, B, T, n)
@@ -674,7 +674,7 @@ class ALSolveDevice(torch.autograd.Function):
         resn, status = torch.empty(B, **kw), torch.empty(B, **kw)
         L = torch.empty(int(lib.dqp_al_banded_factor_bytes(ctypes.byref(dims), dyn.id)) // 8, **kw)
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8 + 1, **kw)
+        ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8, **kw)
         if x_lower is not None:
             assert not fused and ncon == T * n + 2 * T * m + 2 * T * n
             xbd = bounds_layout(x_lower, x_upper, B, T, n)

@@ -1367,9 +1367,11 @@ static size_t al_solve_doubles(int n, int m, int T)
 __attribute__((visibility("default"))) size_t dqp_al_newton_solve_bytes(const dqp_al_mpc_dims *d, int32_t banded)
 {
     if (!d || d->nbatch <= 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return 0;
+    // exactly what newton_solve_impl carves (include/dqp.h, "Extents"): the last array, info, is nbatch int32 in a slot of
+    // nbatch doubles, so every array before it starts on a multiple of 8 bytes and nothing lies behind it
     if (banded)         // update + 20 candidate merits + current merit + info per problem
-        return ((size_t)d->nbatch * ((size_t)d->T * (d->n_state + d->n_ctrl) + 20 + 1 + 1) + 2) * sizeof(double);
-    return ((size_t)d->nbatch * al_solve_doubles(d->n_state, d->n_ctrl, d->T) + 2) * sizeof(double);
+        return (size_t)d->nbatch * ((size_t)d->T * (d->n_state + d->n_ctrl) + 20 + 1 + 1) * sizeof(double);
+    return (size_t)d->nbatch * al_solve_doubles(d->n_state, d->n_ctrl, d->T) * sizeof(double);
 }
 
 static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,

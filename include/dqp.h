@@ -152,6 +152,24 @@ typedef struct dqp_opts {
 int dqp_version(void);
 const char *dqp_error_string(int code);
 
+/*
+ * Extents.  What holds for every entry point of this header that takes device pointers:
+ *   - an array argument is read and written only inside the extent its documented shape declares, from its first
+ *     byte to its last, and a workspace / termination / factor / scratch buffer only inside the bytes its size function
+ *     (the `*_bytes` functions: dqp_workspace_bytes, dqp_termination_bytes, dqp_qp_backward_shared_bytes,
+ *     dqp_mpc_qp_workspace_bytes, dqp_mpc_qp_termination_bytes, dqp_mpc_qp_stepped_workspace_bytes,
+ *     dqp_mpc_qp_stepped_termination_bytes, dqp_mpc_sqp_workspace_bytes, dqp_al_newton_solve_bytes,
+ *     dqp_al_mpc_solve_bytes, dqp_al_mpc_solve_fused_bytes[_bounds], dqp_al_banded_factor_bytes,
+ *     dqp_al_banded_jac_factor_bytes, dqp_deq_partial_bytes, and their `_xbounds` twins) returns for the same `dims`
+ *     and `opts`: exactly that many bytes suffice, no slack has to be added, and 8-byte alignment is enough unless the
+ *     entry says otherwise;
+ *   - the kernels pack 2, 4 or 8 problems (or rows) into a wavefront; in a batch that is no multiple of that, the idle
+ *     lanes neither load nor store outside these extents;
+ *   - no result depends on a byte outside them (nor on what a workspace held before the call).
+ * tests/test_gpu_guardband.py runs every family between guard bands at exactly these sizes; DESIGN.md ("Extents and
+ * size functions") lists each size function beside the launcher that carves its buffer.
+ */
+
 /* Bytes of caller-provided device workspace for dqp_qp_forward (8-byte aligned).  Optional:
  * with workspace == NULL, or a size for which this returns 0, every solver state lives in
  * LDS/registers.  With it, the size-specialised forward kernels eliminate the equality
@@ -493,7 +511,11 @@ int dqp_al_merit(const dqp_al_mpc_dims *dims, int32_t ncand, const double *xu, c
  * Dense form (banded == 0): n_state <= 8, n_ctrl <= 2, nz <= 128, L is (B,nz,nz).
  * Banded form (banded != 0): n_state <= 12, n_state + n_ctrl <= 16, any T (BASELINE config 4:
  * n 12, m 4, T 30, nz 480); L is the buffer of dqp_al_banded_factor_bytes (see below).
- * The workspace size depends on the form.
+ * The workspace size depends on the form: banded, 8 * nbatch * (T (n_state + n_ctrl) + 22) bytes -- per problem the
+ * update, the 20 candidate merits, the current merit and one double's room for the int32 pivot flag; dense, 8 * nbatch *
+ * ((T-1) n^2 + (T-1) n m + ncon + ncon nz + 2 nz + 22) with n = n_state, m = n_ctrl, nz = T (n + m), ncon = T n + 2 T m
+ * (the Jacobians, the residual, the constraint Jacobian, gradient and update before the same tail).  That is the whole
+ * carve: earlier versions reported 16 bytes more, which no launch touched.
  */
 size_t dqp_al_newton_solve_bytes(const dqp_al_mpc_dims *dims, int32_t banded);
 int dqp_al_newton_solve(const dqp_al_mpc_dims *dims, int dyn_id, double dt, int32_t n_steps, int32_t banded,
