@@ -34,10 +34,7 @@ namespace dqp { extern unsigned long long *g_debug_stamps; }
 
 namespace {
 
-using dqp::StridedBounds;
-using dqp::strided_bounds;
-using dqp::BoxBounds;
-using dqp::box_bounds;
+using namespace dqp;        // the bound families (dqp_al_bounds.h), the host layer (dqp_al_host.h)
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -704,6 +701,14 @@ struct LsAPS : LsAP { long long bsb, bst; };
 struct LsAPX : LsAPS { const double *xlo, *xhi; long long xsb, xst; };
 template <class Map> using LsArg =
     std::conditional_t<box_bounds<Map>::value, LsAPX, std::conditional_t<strided_bounds<Map>::value, LsAPS, LsAP>>;
+// the merit of `ncand` candidates xu + 2^-k upd into `merit` (ncand = 0: of xu itself).  The folded selection (xu_w,
+// merit_cur, status, fail, info) is the caller's to set.
+LsAPX ls_args(const AlProblem &v, const double *xu, const double *upd, double *merit, int ncand)
+{
+    LsAPX P = dqp::boxed_args<LsAPX>(v);
+    P.xu = xu; P.upd = upd; P.merit = merit; P.dt = v.dt; P.n = v.n; P.m = v.m; P.ncand = ncand; P.dyn = v.model;
+    return P;
+}
 
 // merit (al_utils.py:37-59) of ncand candidates xu + 2^-k upd per problem (x_0 pinned to x0,
 // al_utils.py:515), dynamics evaluated in the kernel; 16 lanes per (candidate, problem).  ncand = 0
@@ -1002,16 +1007,12 @@ template <class Map> int launch_ls_t(const LsAPX &P, hipStream_t st)
     return DQP_OK;
 }
 
-template <class Model> int launch_ls_layout(const LsAPX &P, hipStream_t st)
-{
-    if (P.xlo) return launch_ls_t<BoxBounds<Model>>(P, st);         // a state box: both boxes strided
-    return (P.bsb != 0 || P.bst != 0) ? launch_ls_t<StridedBounds<Model>>(P, st) : launch_ls_t<Model>(P, st);
-}
-
 int launch_ls(const LsAPX &P, hipStream_t st)
 {
     return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
-        return launch_ls_layout<typename decltype(model)::Map>(P, st);
+        using Map = typename decltype(model)::Map;
+        if (P.xlo) return launch_ls_t<BoxBounds<Map>>(P, st);         // a state box: both boxes strided
+        return (P.bsb != 0 || P.bst != 0) ? launch_ls_t<StridedBounds<Map>>(P, st) : launch_ls_t<Map>(P, st);
     });
 }
 
@@ -1025,6 +1026,14 @@ struct OutP {
     const double *xlo, *xhi;    // state box, read by the BoxBounds<> instantiations only (else NULL); lam / lam_new then
     long long xsb, xst;         // carry 2 T n more rows
 };
+// lam_new <- the multiplier update of v.lam at xu; rho_next: optional
+OutP out_args(const AlProblem &v, const double *xu, double *lam_new, double *cost, double *resn, double *rho_next)
+{
+    OutP P = dqp::boxed_args<OutP>(v);
+    P.xu = xu; P.lam_new = lam_new; P.cost = cost; P.resn = resn; P.rho_next = rho_next;
+    P.dt = v.dt; P.n = v.n; P.m = v.m; P.dyn = v.model;
+    return P;
+}
 
 // Between two AL iterations (qpth/AL_mpc.py:296-307): res = constraint residual at the new iterate,
 // lam <- lam + rho res with the inequality block clamped at 0, cost of the iterate and the norm of
@@ -1191,7 +1200,7 @@ int launch_outer(const OutP &P, hipStream_t st)
         if (P.xlo) DQP_LAUNCH(al_outer_kernel<BoxBounds<Map>>, grid, block, 0, st, P);
         else if (P.bsb != 0 || P.bst != 0) DQP_LAUNCH(al_outer_kernel<StridedBounds<Map>>, grid, block, 0, st, P);
         else DQP_LAUNCH(al_outer_kernel<Map>, grid, block, 0, st, P);
-        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+        return launched();
     });
 }
 
@@ -1243,23 +1252,53 @@ int launch(K kernel, const AlP &P, size_t lds, void *stream, int threads = 256)
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return DQP_ERR_LAUNCH;
     DQP_LAUNCH(kernel, dim3(P.B), dim3(threads), lds, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return launched();
 }
 
 // the dense Newton step: al_newton_kernel at the number of 16-column slots nz takes
 int launch_newton(const AlP &P, size_t lds, void *stream)
 {
-    switch ((P.nz + 15) / 16) {
-    case 1: return launch(al_newton_kernel<1>, P, lds, stream);
-    case 2: return launch(al_newton_kernel<2>, P, lds, stream);
-    case 3: return launch(al_newton_kernel<3>, P, lds, stream);
-    case 4: return launch(al_newton_kernel<4>, P, lds, stream);
-    case 5: return launch(al_newton_kernel<5>, P, lds, stream);
-    case 6: return launch(al_newton_kernel<6>, P, lds, stream);
-    case 7: return launch(al_newton_kernel<7>, P, lds, stream);
-    default: return launch(al_newton_kernel<8>, P, lds, stream);
-    }
+    static constexpr decltype(&al_newton_kernel<1>) kernels[8] = {
+        al_newton_kernel<1>, al_newton_kernel<2>, al_newton_kernel<3>, al_newton_kernel<4>,
+        al_newton_kernel<5>, al_newton_kernel<6>, al_newton_kernel<7>, al_newton_kernel<8>};
+    const int slots = (P.nz + 15) / 16;         // 1 .. 8 behind fill(); anything else takes the largest, as it always did
+    return launch(kernels[slots >= 1 && slots < 8 ? slots - 1 : 7], P, lds, stream);
 }
+
+// The workspace of dqp_al_newton_solve in its two forms (include/dqp.h, "Extents"), carved and sized from ONE member
+// list.  The last array, info, is nbatch int32 in a slot of nbatch doubles, so every array before it starts on a multiple
+// of 8 bytes and nothing lies behind it.
+constexpr int N_LINESEARCH = 20;                // line-search candidates 2^-k, k = 0 .. 19 (al_utils.py:503-527)
+struct NewtonWork {
+    double *Jx, *Ju, *resc, *Jc, *grad;         // the dense form only
+    double *upd, *merit, *merit_cur;            // update, N_LINESEARCH candidate merits, current merit
+    int32_t *info;
+    size_t doubles;                             // of the form, per problem
+};
+// The arrays of a batch of B at `base`, in the order they lie; (NULL, 0): the size alone
+NewtonWork newton_work(void *base, size_t B, bool banded, size_t n, size_t m, size_t T)
+{
+    const size_t nz = T * (n + m), ncon = T * n + 2 * T * m;
+    NewtonWork w = {};
+    auto take = [&](auto *&array, size_t per_problem) {
+        array = reinterpret_cast<std::remove_reference_t<decltype(array)>>((double *)base + B * w.doubles);
+        w.doubles += per_problem;
+    };
+    if (!banded) { take(w.Jx, (T - 1) * n * n); take(w.Ju, (T - 1) * n * m); take(w.resc, ncon); take(w.Jc, ncon * nz); take(w.grad, nz); }
+    take(w.upd, nz); take(w.merit, N_LINESEARCH); take(w.merit_cur, 1); take(w.info, 1);
+    return w;
+}
+
+// What dqp_al_newton_solve takes besides the problem, in the order of its prototype
+struct NewtonIo {
+    int32_t n_steps;
+    double *xu, *L, *status;
+    int32_t *fail;
+    void *workspace;
+    bool clear_fail = true;     // false: the caller's own kernel zeroed the flag (dqp_al_mpc_solve: al_start_kernel clears all)
+    bool keep_factor = true;    // false: nobody reads L after this call (only the last solve's last factor is used,
+                                // NewtonAL.backward, al_utils.py:477-480)
+};
 
 }  // namespace
 
@@ -1299,9 +1338,25 @@ dqp_al_assemble(const dqp_al_mpc_dims *d, const double *Jx, const double *Ju, co
     if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return DQP_ERR_BAD_ARG;
     if (d->nbatch == 0) return DQP_OK;
     if (!Jx || !Ju || !res_c || (gterm && (!lam || !rho))) return DQP_ERR_BAD_ARG;
-    AsmP P = {Jx, Ju, lam, res_c, rho, Jc, gterm, d->nbatch, d->n_state, d->n_ctrl, d->T, nullptr, nullptr, nullptr};
+    AsmP P = {};        // no Qd, q, xu: gterm without the cost's share
+    P.Jx = Jx; P.Ju = Ju; P.lam = lam; P.resc = res_c; P.rho = rho; P.Jc = Jc; P.gterm = gterm;
+    P.B = d->nbatch; P.n = d->n_state; P.m = d->n_ctrl; P.T = d->T;
     DQP_LAUNCH(al_assemble_kernel, dim3(P.B), dim3(256), 0, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return launched();
+}
+
+// Both merit entries behind their front checks.  A kernel without state rows or strides gets the MeritPS / MeritP part of P.
+static int merit_launch(const AlProblem &v, int32_t ncand, const double *xu, const double *x_next, double *merit)
+{
+    if (ncand == 0) return DQP_OK;
+    if (const int r = v.ready(xu && x_next && merit); r != 1) return r;
+    MeritPX P = dqp::boxed_args<MeritPX>(v);
+    P.xu = xu; P.xn = x_next; P.merit = merit; P.n = v.n; P.m = v.m; P.ncand = ncand;
+    const dim3 grid((unsigned)(((long long)ncand * v.B + 15) / 16));
+    if (!v.has_x && v.strided()) DQP_LAUNCH(al_merit_kernel<true>, grid, dim3(256), 0, v.stream, static_cast<const MeritPS &>(P));
+    else if (!v.has_x) DQP_LAUNCH(al_merit_kernel<false>, grid, dim3(256), 0, v.stream, static_cast<const MeritP &>(P));
+    else DQP_LAUNCH((al_merit_kernel<true, true>), grid, dim3(256), 0, v.stream, P);
+    return launched();
 }
 
 __attribute__((visibility("default"))) int
@@ -1309,20 +1364,8 @@ dqp_al_merit_bounds(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, c
                     const double *x0, const double *Qdiag, const double *q, const double *lam,
                     const double *rho, const dqp_al_bounds *bounds, double *merit, void *stream)
 {
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || ncand < 0) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0 || ncand == 0) return DQP_OK;
-    if (!xu || !x_next || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !merit)
-        return DQP_ERR_BAD_ARG;
-    MeritPS P = {{xu, x_next, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, merit, d->nbatch, d->n_state,
-                 d->n_ctrl, d->T, ncand}, (long long)bounds->stride_b, (long long)bounds->stride_t};
-    const long long total = (long long)ncand * d->nbatch;
-    if (dqp::al_bounds_strided(bounds))
-        DQP_LAUNCH(al_merit_kernel<true>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream, P);
-    else
-        DQP_LAUNCH(al_merit_kernel<false>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
-                   static_cast<const MeritP &>(P));
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    if (dqp::al_bounds_check(d, bounds) || ncand < 0) return DQP_ERR_BAD_ARG;
+    return merit_launch(dqp::al_problem(d, 0, 0.0, x0, Qdiag, q, lam, rho, bounds, nullptr, stream), ncand, xu, x_next, merit);
 }
 
 // The merit with state rows (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per problem; any (n_state, n_ctrl)
@@ -1332,19 +1375,9 @@ dqp_al_merit_xbounds(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, 
                      const double *rho, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *merit,
                      void *stream)
 {
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || ncand < 0) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK || dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK)
-        return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0 || ncand == 0) return DQP_OK;
-    if (!xu || !x_next || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !xbounds->lower ||
-        !xbounds->upper || !merit)
-        return DQP_ERR_BAD_ARG;
-    MeritPX P = {{{xu, x_next, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, merit, d->nbatch, d->n_state,
-                   d->n_ctrl, d->T, ncand}, (long long)bounds->stride_b, (long long)bounds->stride_t},
-                 xbounds->lower, xbounds->upper, (long long)xbounds->stride_b, (long long)xbounds->stride_t};
-    const long long total = (long long)ncand * d->nbatch;
-    DQP_LAUNCH((al_merit_kernel<true, true>), dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    // no model and any (n_state, n_ctrl): the sizes and both layouts, not al_xbounds_check
+    if (dqp::al_bounds_check(d, bounds) || dqp::al_box_layout(xbounds, d, d->n_state) || ncand < 0) return DQP_ERR_BAD_ARG;
+    return merit_launch(dqp::al_problem(d, 0, 0.0, x0, Qdiag, q, lam, rho, bounds, xbounds, stream), ncand, xu, x_next, merit);
 }
 
 __attribute__((visibility("default"))) int
@@ -1357,28 +1390,80 @@ dqp_al_merit(const dqp_al_mpc_dims *d, int32_t ncand, const double *xu, const do
 }
 
 
-// workspace of dqp_al_newton_solve, in doubles per problem (see the carve below)
-static size_t al_solve_doubles(int n, int m, int T)
-{
-    const size_t nt = n + m, nz = (size_t)T * nt, ncon = (size_t)T * n + 2 * (size_t)T * m;
-    return (size_t)(T - 1) * n * n + (size_t)(T - 1) * n * m + ncon + ncon * nz + nz + nz + 20 + 1 + 1;
-}
-
 __attribute__((visibility("default"))) size_t dqp_al_newton_solve_bytes(const dqp_al_mpc_dims *d, int32_t banded)
 {
     if (!d || d->nbatch <= 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return 0;
-    // exactly what newton_solve_impl carves (include/dqp.h, "Extents"): the last array, info, is nbatch int32 in a slot of
-    // nbatch doubles, so every array before it starts on a multiple of 8 bytes and nothing lies behind it
-    if (banded)         // update + 20 candidate merits + current merit + info per problem
-        return (size_t)d->nbatch * ((size_t)d->T * (d->n_state + d->n_ctrl) + 20 + 1 + 1) * sizeof(double);
-    return (size_t)d->nbatch * al_solve_doubles(d->n_state, d->n_ctrl, d->T) * sizeof(double);
+    return (size_t)d->nbatch * newton_work(nullptr, 0, banded != 0, d->n_state, d->n_ctrl, d->T).doubles * sizeof(double);
 }
 
-static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
-                             const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
-                             const dqp_al_bounds *bounds, double *xu, double *L, double *status,
-                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor = true,
-                             const dqp_al_bounds *xb = nullptr);
+// What the two Newton loops share: the arguments of the candidates' line search and of the selection, the failure flag
+// cleared, the merit at the start
+static int newton_start(const AlProblem &v, const NewtonIo &o, const NewtonWork &w, LsAPX &Lc, SelP &Se)
+{
+    Lc = ls_args(v, o.xu, w.upd, w.merit, N_LINESEARCH);
+    Se.merit = w.merit; Se.upd = w.upd; Se.x0 = v.x0; Se.xu = o.xu; Se.merit_cur = w.merit_cur; Se.status = o.status;
+    Se.fail = o.fail; Se.info = w.info; Se.B = v.B; Se.n = v.n; Se.nz = v.nz(); Se.ncand = N_LINESEARCH;
+    if (o.clear_fail && hipMemsetAsync(o.fail, 0, sizeof(int32_t), v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
+    return launch_ls(ls_args(v, o.xu, w.upd, w.merit_cur, 0), v.stream);
+}
+
+// Block-tridiagonal form (dqp_al_banded.hip): linearise + gradient + block Cholesky + solve in ONE launch per step, no
+// Jacobian / Hessian in HBM; L receives the banded factor.  The only form that takes a state box.
+static int newton_banded(const AlProblem &v, const NewtonIo &o)
+{
+    if (!v.model_ok()) return DQP_ERR_BAD_ARG;
+    if (v.too_large()) return DQP_ERR_TOO_LARGE;
+    if (!o.L) return DQP_ERR_BAD_ARG;
+    const NewtonWork w = newton_work(o.workspace, v.B, true, v.n, v.m, v.T);
+    LsAPX Lc;
+    SelP Se;
+    int rc = newton_start(v, o, w, Lc, Se);
+    if (rc) return rc;
+    // the selection folded into the line search where one group sees all candidates of its problem
+    Lc.xu_w = o.xu; Lc.merit_cur = w.merit_cur; Lc.status = o.status; Lc.fail = o.fail; Lc.info = w.info;
+    for (int it = 0; it < o.n_steps; ++it) {
+        if ((rc = al_banded_newton_step(v, o.xu, w.upd, o.L, w.info, it == o.n_steps - 1 && o.keep_factor)) != DQP_OK) return rc;
+        rc = launch_ls(Lc, v.stream);
+        if (rc != DQP_OK && rc != 2) return rc;
+        // candidates split over several groups: select in a launch of its own
+        if (rc != 2) DQP_LAUNCH(al_select_kernel, dim3(v.B), dim3(64), 0, v.stream, Se);
+    }
+    return launched();
+}
+
+// Dense form: Jacobians, the assembled Jc and the nz x nz factor in HBM / LDS; control bounds only
+static int newton_dense(const AlProblem &v, const NewtonIo &o)
+{
+    if (!v.model_ok()) return DQP_ERR_BAD_ARG;
+    if (v.n > 8 || v.m > 2) return DQP_ERR_TOO_LARGE;
+    const dqp_al_dims ad = {v.B, v.nz(), (int)v.ncon(), 0};
+    AlP A = {};
+    size_t lds = 0;
+    int rc = fill(&ad, A, lds);
+    if (rc) return rc;
+    const NewtonWork w = newton_work(o.workspace, v.B, false, v.n, v.m, v.T);
+    A.Jc = w.Jc; A.Qd = v.Qd; A.rho = v.rho; A.grad = w.grad; A.update = w.upd; A.L = o.L; A.info = w.info;
+    LsAPX Lc;
+    SelP Se;
+    if ((rc = newton_start(v, o, w, Lc, Se)) != DQP_OK) return rc;
+    // the clamped box rows carry the bound layout; the dense assembly and factorisation read them
+    LinPS Li = {};
+    Li.xu = o.xu; Li.x0 = v.x0; Li.ul = v.u.lower; Li.uu = v.u.upper; Li.Jx = w.Jx; Li.Ju = w.Ju; Li.resc = w.resc;
+    Li.dt = v.dt; Li.B = v.B; Li.n = v.n; Li.m = v.m; Li.T = v.T; Li.dyn = v.model; Li.bsb = v.u.stride_b; Li.bst = v.u.stride_t;
+    const dim3 lin_grid((unsigned)(((long long)v.B * v.T + 255) / 256));
+    AsmP As = {};
+    As.Jx = w.Jx; As.Ju = w.Ju; As.lam = v.lam; As.resc = w.resc; As.rho = v.rho; As.Jc = w.Jc; As.gterm = w.grad;
+    As.B = v.B; As.n = v.n; As.m = v.m; As.T = v.T; As.Qd = v.Qd; As.q = v.q; As.xu = o.xu;
+    for (int it = 0; it < o.n_steps; ++it) {
+        if (v.strided()) DQP_LAUNCH(al_linearize_kernel<true>, lin_grid, dim3(256), 0, v.stream, Li);
+        else DQP_LAUNCH(al_linearize_kernel<false>, lin_grid, dim3(256), 0, v.stream, static_cast<const LinP &>(Li));
+        DQP_LAUNCH(al_assemble_kernel, dim3(v.B), dim3(256), 0, v.stream, As);
+        if ((rc = launch_newton(A, lds, v.stream)) != DQP_OK) return rc;
+        if ((rc = launch_ls(Lc, v.stream)) != DQP_OK) return rc;
+        DQP_LAUNCH(al_select_kernel, dim3(v.B), dim3(64), 0, v.stream, Se);
+    }
+    return launched();
+}
 
 __attribute__((visibility("default"))) int
 dqp_al_newton_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
@@ -1386,8 +1471,10 @@ dqp_al_newton_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int3
                            const dqp_al_bounds *bounds, double *xu, double *L, double *status,
                            int32_t *fail, void *workspace, void *stream)
 {
-    return newton_solve_impl(d, dyn_id, dt, n_steps, banded, x0, Qdiag, q, lam, rho, bounds, xu, L, status, fail,
-                             workspace, stream, true);
+    if (dqp::al_bounds_check(d, bounds) || n_steps < 1) return DQP_ERR_BAD_ARG;
+    const AlProblem v = dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam, rho, bounds, nullptr, stream);
+    if (const int r = v.ready(xu && fail && workspace); r != 1) return r;
+    return (banded ? newton_banded : newton_dense)(v, {n_steps, xu, L, status, fail, workspace});
 }
 
 __attribute__((visibility("default"))) int
@@ -1401,99 +1488,6 @@ dqp_al_newton_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_s
                                       workspace, stream);
 }
 
-// clear_fail = false: the caller's own kernel zeroed the flag (dqp_al_mpc_solve: al_start_kernel clears all of them);
-// xb: the state box of the `_xbounds` entries (block-tridiagonal form only; the caller checked its layout), else NULL
-static int newton_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t n_steps, int32_t banded,
-                             const double *x0, const double *Qdiag, const double *q, const double *lam, const double *rho,
-                             const dqp_al_bounds *bounds, double *xu, double *L, double *status,
-                             int32_t *fail, void *workspace, void *stream, bool clear_fail, bool keep_factor,
-                             const dqp_al_bounds *xb)
-{
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || n_steps < 1) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    const long long bsb = bounds->stride_b, bst = bounds->stride_t;
-    if (!x0 || !Qdiag || !q || !lam || !rho || !u_lower || !u_upper || !xu || !fail || !workspace) return DQP_ERR_BAD_ARG;
-    if (xb && (!xb->lower || !xb->upper || !banded)) return DQP_ERR_BAD_ARG;
-    const double *xlo = xb ? xb->lower : nullptr, *xhi = xb ? xb->upper : nullptr;
-    const long long xsb = xb ? xb->stride_b : 0, xst = xb ? xb->stride_t : 0;
-    const int B = d->nbatch, n = d->n_state, m = d->n_ctrl, T = d->T, nt = n + m, nz = T * nt;
-    const int ncon = T * n + 2 * T * m;
-    hipStream_t st = (hipStream_t)stream;
-    double *w = (double *)workspace;
-    if (banded) {
-        // block-tridiagonal form (dqp_al_banded.hip): linearise + gradient + block Cholesky + solve in
-        // ONE launch per step, no Jacobian / Hessian in HBM; L receives the banded factor
-        if (nt > 16 || n > 12) return DQP_ERR_TOO_LARGE;
-        if (!L) return DQP_ERR_BAD_ARG;
-        double *upd = w;           w += (size_t)B * nz;
-        double *merit = w;         w += (size_t)20 * B;
-        double *merit_cur = w;     w += (size_t)B;
-        int32_t *info = (int32_t *)w;
-        if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-        LsAPX Lp = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst},
-                    xlo, xhi, xsb, xst};
-        int rc0 = launch_ls(Lp, st);                                    // merit at the start
-        if (rc0) return rc0;
-        for (int it = 0; it < n_steps; ++it) {
-            // only the last step's factor is used afterwards (NewtonAL.backward, al_utils.py:477-480)
-            int rc = dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, upd, L, info,
-                                                            stream, (it == n_steps - 1 && keep_factor) ? 1 : 0, xb);
-            if (rc) return rc;
-            LsAPX Lc = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id,
-                          xu, merit_cur, status, fail, info}, bsb, bst}, xlo, xhi, xsb, xst};
-            rc = launch_ls(Lc, st);
-            if (rc != DQP_OK && rc != 2) return rc;
-            if (rc != 2) {          // candidates split over several groups: select in a launch of its own
-                SelP Se = {merit, upd, x0, xu, merit_cur, status, fail, info, B, n, nz, 20};
-                DQP_LAUNCH(al_select_kernel, dim3(B), dim3(64), 0, st, Se);
-            }
-        }
-        return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-    }
-    if (d->n_state > 8 || d->n_ctrl > 2) return DQP_ERR_TOO_LARGE;
-    dqp_al_dims ad = {B, nz, ncon, 0};
-    AlP A = {};
-    size_t lds = 0;
-    int rc = fill(&ad, A, lds);
-    if (rc) return rc;
-    double *Jx = w;            w += (size_t)B * (T - 1) * n * n;
-    double *Ju = w;            w += (size_t)B * (T - 1) * n * m;
-    double *resc = w;          w += (size_t)B * ncon;
-    double *Jc = w;            w += (size_t)B * ncon * nz;
-    double *grad = w;          w += (size_t)B * nz;
-    double *upd = w;           w += (size_t)B * nz;
-    double *merit = w;         w += (size_t)20 * B;
-    double *merit_cur = w;     w += (size_t)B;
-    int32_t *info = (int32_t *)w;
-    if (clear_fail && hipMemsetAsync(fail, 0, sizeof(int32_t), st) != hipSuccess) return DQP_ERR_LAUNCH;
-    LsAPX Lp = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit_cur, dt, B, n, m, T, 0, dyn_id}, bsb, bst}};
-    rc = launch_ls(Lp, st);                                             // merit at the start
-    if (rc) return rc;
-    for (int it = 0; it < n_steps; ++it) {
-        LinPS Li = {{xu, x0, u_lower, u_upper, Jx, Ju, resc, dt, B, n, m, T, dyn_id}, bsb, bst};
-        if (bsb != 0 || bst != 0)       // the clamped box rows carry the layout; the dense assembly and factorisation read them
-            DQP_LAUNCH(al_linearize_kernel<true>, dim3((unsigned)(((long long)B * T + 255) / 256)), dim3(256), 0, st, Li);
-        else
-            DQP_LAUNCH(al_linearize_kernel<false>, dim3((unsigned)(((long long)B * T + 255) / 256)), dim3(256), 0, st,
-                       static_cast<const LinP &>(Li));
-        AsmP As = {Jx, Ju, lam, resc, rho, Jc, grad, B, n, m, T, Qdiag, q, xu};
-        DQP_LAUNCH(al_assemble_kernel, dim3(B), dim3(256), 0, st, As);
-        AlP P = A;
-        P.Jc = Jc; P.Qd = Qdiag; P.rho = rho; P.grad = grad; P.update = upd; P.L = L; P.info = info;
-        rc = launch_newton(P, lds, stream);
-        if (rc) return rc;
-        LsAPX Lc = {{{xu, upd, x0, Qdiag, q, lam, rho, u_lower, u_upper, merit, dt, B, n, m, T, 20, dyn_id}, bsb, bst}};
-        rc = launch_ls(Lc, st);
-        if (rc) return rc;
-        SelP Se = {merit, upd, x0, xu, merit_cur, status, fail, info, B, n, nz, 20};
-        DQP_LAUNCH(al_select_kernel, dim3(B), dim3(64), 0, st, Se);
-    }
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
-}
-
 
 __attribute__((visibility("default"))) int
 dqp_al_outer_update(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
@@ -1505,26 +1499,14 @@ dqp_al_outer_update(const dqp_al_mpc_dims *d, int dyn_id, double dt, const doubl
     return dqp_al_outer_update_bounds(d, dyn_id, dt, xu, x0, lam, rho, Qdiag, q, &bd, lam_new, cost, res_norm, stream);
 }
 
-// xb: the state box of dqp_al_outer_update_xbounds (its layout checked by the caller), else NULL
-static int outer_update_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
-                             const double *lam, const double *rho, const double *Qdiag, const double *q,
-                             const dqp_al_bounds *bounds, const dqp_al_bounds *xb, double *lam_new, double *cost,
-                             double *res_norm, void *stream)
+// behind either front check.  The model in front of the limit, the limit in front of the buffers.
+static int outer_update(const AlProblem &v, const double *xu, double *lam_new, double *cost, double *res_norm)
 {
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
-    if (d->n_state > 12 || d->n_state + d->n_ctrl > 16) return DQP_ERR_TOO_LARGE;
-    if (!xu || !x0 || !lam || !rho || !Qdiag || !q || !u_lower || !u_upper || !lam_new || !cost || !res_norm)
-        return DQP_ERR_BAD_ARG;
-    if (xb && (!xb->lower || !xb->upper)) return DQP_ERR_BAD_ARG;
-    OutP P = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, lam_new, cost, res_norm, dt, d->nbatch, d->n_state,
-              d->n_ctrl, d->T, dyn_id, nullptr, (long long)bounds->stride_b, (long long)bounds->stride_t,
-              xb ? xb->lower : nullptr, xb ? xb->upper : nullptr, xb ? (long long)xb->stride_b : 0,
-              xb ? (long long)xb->stride_t : 0};
-    return launch_outer(P, (hipStream_t)stream);
+    if (v.B == 0) return DQP_OK;
+    if (!v.model_ok()) return DQP_ERR_BAD_ARG;
+    if (v.too_large()) return DQP_ERR_TOO_LARGE;
+    if (!v.inputs_set() || !xu || !lam_new || !cost || !res_norm) return DQP_ERR_BAD_ARG;
+    return launch_outer(out_args(v, xu, lam_new, cost, res_norm, nullptr), v.stream);
 }
 
 __attribute__((visibility("default"))) int
@@ -1532,7 +1514,8 @@ dqp_al_outer_update_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, cons
                            const double *lam, const double *rho, const double *Qdiag, const double *q,
                            const dqp_al_bounds *bounds, double *lam_new, double *cost, double *res_norm, void *stream)
 {
-    return outer_update_impl(d, dyn_id, dt, xu, x0, lam, rho, Qdiag, q, bounds, nullptr, lam_new, cost, res_norm, stream);
+    if (dqp::al_bounds_check(d, bounds)) return DQP_ERR_BAD_ARG;
+    return outer_update(dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam, rho, bounds, nullptr, stream), xu, lam_new, cost, res_norm);
 }
 
 __attribute__((visibility("default"))) int
@@ -1541,9 +1524,8 @@ dqp_al_outer_update_xbounds(const dqp_al_mpc_dims *d, int model, double dt, cons
                             const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *lam_new, double *cost,
                             double *res_norm, void *stream)
 {
-    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
-    if (rc) return rc;
-    return outer_update_impl(d, model, dt, xu, x0, lam, rho, Qdiag, q, bounds, xbounds, lam_new, cost, res_norm, stream);
+    if (const int rc = al_xbounds_check(d, bounds, xbounds, d && dyn::model_matches(model, d->n_state, d->n_ctrl))) return rc;
+    return outer_update(dqp::al_problem(d, model, dt, x0, Qdiag, q, lam, rho, bounds, xbounds, stream), xu, lam_new, cost, res_norm);
 }
 
 __attribute__((visibility("default"))) int32_t dqp_al_ncon_xbounds(const dqp_al_mpc_dims *d)
@@ -1568,10 +1550,11 @@ dqp_al_newton_solve_xbounds(const dqp_al_mpc_dims *d, int model, double dt, int3
                             const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *xu, double *L,
                             double *status, int32_t *fail, void *workspace, void *stream)
 {
-    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
-    if (rc) return rc;
-    return newton_solve_impl(d, model, dt, n_steps, 1, x0, Qdiag, q, lam, rho, bounds, xu, L, status, fail, workspace,
-                             stream, true, true, xbounds);
+    if (const int rc = al_xbounds_check(d, bounds, xbounds, d && dyn::model_matches(model, d->n_state, d->n_ctrl))) return rc;
+    if (n_steps < 1) return DQP_ERR_BAD_ARG;
+    const AlProblem v = dqp::al_problem(d, model, dt, x0, Qdiag, q, lam, rho, bounds, xbounds, stream);
+    if (const int r = v.ready(xu && fail && workspace); r != 1) return r;
+    return newton_banded(v, {n_steps, xu, L, status, fail, workspace});        // block-tridiagonal only
 }
 
 __attribute__((visibility("default"))) size_t dqp_al_mpc_solve_bytes(const dqp_al_mpc_dims *d)
@@ -1593,46 +1576,33 @@ dqp_al_mpc_solve(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_ite
                                    status, fail, workspace, stream);
 }
 
-// xb: the state box of dqp_al_mpc_solve_xbounds (its layout checked by the caller), else NULL
-static int mpc_solve_impl(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t al_iter, int32_t newton_steps,
-                          const double *x_init, const double *u_init, const double *x0, const double *Qdiag, const double *q,
-                          const dqp_al_bounds *bounds, const dqp_al_bounds *xb, const double *lam_in, const double *rho_in,
-                          const double *prev_cost, const double *prev_lam, const double *prev_rho, int32_t n_prev,
-                          double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
-                          double *status, int32_t *fail, void *workspace, void *stream)
+// Behind either front check; v.lam / v.rho: lam_in / rho_in.  The model is not checked here: the first Newton solve
+// refuses an unregistered one, behind the start kernel.
+static int mpc_solve(const AlProblem &v, const AlMpcIo &io)
 {
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
-        n_prev < 0)
-        return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!x_init || !u_init || !x0 || !Qdiag || !q || !u_lower || !u_upper || !lam_in || !rho_in || !xu || !hist_cost ||
-        !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
-        return DQP_ERR_BAD_ARG;
-    if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
-    if (xb && (!xb->lower || !xb->upper)) return DQP_ERR_BAD_ARG;
-    if (d->n_state > 12 || d->n_state + d->n_ctrl > 16) return DQP_ERR_TOO_LARGE;
-    const int B = d->nbatch, n = d->n_state, m = d->n_ctrl, T = d->T;
-    const long long ncon = (long long)T * n + 2LL * T * m + (xb ? 2LL * T * n : 0);
-    hipStream_t st = (hipStream_t)stream;
-    StartP S = {x_init, u_init, Qdiag, q, lam_in, rho_in, prev_cost, prev_lam, prev_rho, xu, hist_cost, hist_lam, hist_rho,
-                B, n, m, T, n_prev, fail, al_iter};
-    if (xb) DQP_LAUNCH(al_start_xbounds_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
-    else DQP_LAUNCH(al_start_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, S);
-    for (int i = 0; i < al_iter; ++i) {
-        const double *lam = hist_lam + (long long)i * B * ncon, *rho = hist_rho + (long long)i * B;
-        int rc = newton_solve_impl(d, dyn_id, dt, newton_steps, 1, x0, Qdiag, q, lam, rho, bounds, xu, factor,
-                                   status, fail + i, workspace, stream, false, i == al_iter - 1, xb);
-        if (rc) return rc;
-        OutP O = {xu, x0, lam, rho, Qdiag, q, u_lower, u_upper, hist_lam + (long long)(i + 1) * B * ncon,
-                  hist_cost + (long long)(i + 1) * B, res_norm, dt, B, n, m, T, dyn_id, hist_rho + (long long)(i + 1) * B,
-                  (long long)bounds->stride_b, (long long)bounds->stride_t,
-                  xb ? xb->lower : nullptr, xb ? xb->upper : nullptr, xb ? (long long)xb->stride_b : 0,
-                  xb ? (long long)xb->stride_t : 0};
-        if ((rc = launch_outer(O, st)) != DQP_OK) return rc;
+    if (const int r = v.ready(io.buffers_set()); r != 1) return r;
+    if (v.too_large()) return DQP_ERR_TOO_LARGE;
+    StartP S = {};
+    S.x_init = io.x_init; S.u_init = io.u_init; S.Qd = v.Qd; S.q = v.q; S.lam_in = v.lam; S.rho_in = v.rho;
+    S.hist_cost = io.prev_cost; S.hist_lam = io.prev_lam; S.hist_rho = io.prev_rho; S.K = io.n_prev;
+    S.xu = io.xu; S.cost0 = io.hist_cost; S.lam0 = io.hist_lam; S.rho0 = io.hist_rho; S.fail = io.fail; S.nfail = io.al_iter;
+    S.B = v.B; S.n = v.n; S.m = v.m; S.T = v.T;
+    const dim3 start_grid((unsigned)((v.B + 15) / 16));
+    if (v.has_x) DQP_LAUNCH(al_start_xbounds_kernel, start_grid, dim3(256), 0, v.stream, S);
+    else DQP_LAUNCH(al_start_kernel, start_grid, dim3(256), 0, v.stream, S);
+    AlProblem it = v;           // AL iteration i: the multipliers and the penalty of history row i, row i + 1 written
+    NewtonIo o = {io.newton_steps, io.xu, io.factor, io.status, io.fail, io.workspace};
+    o.clear_fail = false;
+    const long long row = v.B, lam_row = v.B * v.ncon();
+    for (int i = 0; i < io.al_iter; ++i) {
+        it.lam = io.hist_lam + i * lam_row; it.rho = io.hist_rho + i * row;
+        o.fail = io.fail + i; o.keep_factor = i == io.al_iter - 1;
+        if (const int rc = newton_banded(it, o)) return rc;
+        const OutP O = out_args(it, io.xu, io.hist_lam + (i + 1) * lam_row, io.hist_cost + (i + 1) * row, io.res_norm,
+                                io.hist_rho + (i + 1) * row);
+        if (const int rc = launch_outer(O, v.stream)) return rc;
     }
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return launched();
 }
 
 __attribute__((visibility("default"))) int
@@ -1643,9 +1613,10 @@ dqp_al_mpc_solve_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, int32_t
                         double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm, double *factor,
                         double *status, int32_t *fail, void *workspace, void *stream)
 {
-    return mpc_solve_impl(d, dyn_id, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, bounds, nullptr, lam_in, rho_in,
-                          prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status,
-                          fail, workspace, stream);
+    const AlMpcIo io = {al_iter, newton_steps, x_init, u_init, prev_cost, prev_lam, prev_rho, n_prev,
+                        xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, workspace};
+    if (dqp::al_bounds_check(d, bounds) || !io.scalars_ok()) return DQP_ERR_BAD_ARG;
+    return mpc_solve(dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam_in, rho_in, bounds, nullptr, stream), io);
 }
 
 __attribute__((visibility("default"))) int
@@ -1656,11 +1627,11 @@ dqp_al_mpc_solve_xbounds(const dqp_al_mpc_dims *d, int model, double dt, int32_t
                          int32_t n_prev, double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
                          double *factor, double *status, int32_t *fail, void *workspace, void *stream)
 {
-    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
-    if (rc) return rc;
-    return mpc_solve_impl(d, model, dt, al_iter, newton_steps, x_init, u_init, x0, Qdiag, q, bounds, xbounds, lam_in, rho_in,
-                          prev_cost, prev_lam, prev_rho, n_prev, xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status,
-                          fail, workspace, stream);
+    const AlMpcIo io = {al_iter, newton_steps, x_init, u_init, prev_cost, prev_lam, prev_rho, n_prev,
+                        xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, workspace};
+    if (const int rc = al_xbounds_check(d, bounds, xbounds, d && dyn::model_matches(model, d->n_state, d->n_ctrl))) return rc;
+    if (!io.scalars_ok()) return DQP_ERR_BAD_ARG;
+    return mpc_solve(dqp::al_problem(d, model, dt, x0, Qdiag, q, lam_in, rho_in, bounds, xbounds, stream), io);
 }
 
 }  // extern "C"

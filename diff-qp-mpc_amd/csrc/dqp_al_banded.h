@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/dqp.h"
+#include "dqp_al_host.h"
 
 namespace dqp {
 
@@ -22,12 +23,10 @@ int al_banded_box_newton(int n_state, int n_ctrl, const BandP &P, void *stream);
 // dqp_al_banded.hip: a batch of B takes eight problems per wavefront where a knot fits a half row (dqp_al_lane_group)
 bool al_banded_narrow(int B);
 
-// dqp_al_banded.hip: dqp_al_banded_newton_step_bounds with `keep` = does the caller use this step's factor afterwards
-// (the Newton loop of dqp_al.hip keeps the last step's only); `xbounds`: the state box of the `_xbounds` entries, or NULL
-int al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
-                                      const double *Qdiag, const double *q, const double *lam, const double *rho,
-                                      const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info, void *stream,
-                                      int keep, const dqp_al_bounds *xbounds = nullptr);
+// dqp_al_banded.hip: dqp_al_banded_newton_step{,_bounds,_xbounds} behind their front check -- the empty batch, the
+// buffers, the launch for the problem's registered model; `keep` = does the caller use this step's factor afterwards (the Newton loop of
+// dqp_al.hip keeps the last step's only)
+int al_banded_newton_step(const AlProblem &v, const double *xu, double *update, void *factor, int32_t *info, bool keep);
 
 }  // namespace dqp
 #endif

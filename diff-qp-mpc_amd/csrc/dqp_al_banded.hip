@@ -67,11 +67,20 @@ template <class Map> int run_solve(const BandP &P, void *stream)
     if constexpr (half_row<Map>()) {
         if (narrow(P.B)) {
             DQP_LAUNCH((al_banded_solve_kernel<Map, 8>), dim3((P.B + 7) / 8), dim3(64), 0, (hipStream_t)stream, P);
-            return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+            return dqp::launched();
         }
     }
     DQP_LAUNCH((al_banded_solve_kernel<Map, 16>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return dqp::launched();
+}
+
+// The one maker of the Newton kernels' argument; the caller-linearised entries add xnext / Jx / Ju.  Solve-only mode
+// (dqp_al_banded_solve) fills its few members itself.
+BandP band_args(const dqp::AlProblem &v, const double *xu, double *update, void *factor, int32_t *info, bool keep)
+{
+    BandP P = dqp::boxed_args<BandP>(v);
+    P.xu = xu; P.upd = update; P.fac = (double *)factor; P.info = info; P.dt = v.dt; P.keep = keep ? 1 : 0;
+    return P;
 }
 
 bool given_supported(int n, int m) { return visit_pair<BAND_NARROW>(n, m, false, [](auto) { return true; }); }
@@ -119,27 +128,12 @@ __attribute__((visibility("default"))) size_t dqp_al_banded_jac_factor_bytes(con
 
 }  // extern "C"
 
-// dqp_al_banded_newton_step with the caller saying whether it needs this step's factor afterwards (the Newton loop of
-// dqp_al.hip keeps the last step's only)
-int dqp::al_banded_newton_step_keep_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, const double *xu, const double *x0,
-                                           const double *Qdiag, const double *q, const double *lam, const double *rho,
-                                           const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info,
-                                           void *stream, int keep, const dqp_al_bounds *xbounds)
+int dqp::al_banded_newton_step(const AlProblem &v, const double *xu, double *update, void *factor, int32_t *info, bool keep)
 {
-    if (!d || d->nbatch < 0 || d->T < 2) return DQP_ERR_BAD_ARG;
-    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    if (xbounds && dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK) return DQP_ERR_BAD_ARG;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !update || !factor)
-        return DQP_ERR_BAD_ARG;
-    if (xbounds && (!xbounds->lower || !xbounds->upper)) return DQP_ERR_BAD_ARG;
-    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, nullptr, nullptr, nullptr, update,
-               (double *)factor, info, dt, d->nbatch, d->T, keep, (long long)bounds->stride_b, (long long)bounds->stride_t,
-               xbounds ? xbounds->lower : nullptr, xbounds ? xbounds->upper : nullptr,
-               xbounds ? (long long)xbounds->stride_b : 0, xbounds ? (long long)xbounds->stride_t : 0};
-    return visit<int>(dyn_id, DQP_ERR_BAD_ARG, [&](auto model) {
-        return run_newton_layout<typename decltype(model)::Map>(P, stream);
+    if (const int r = v.ready(xu && update && factor); r != 1) return r;        // info is optional
+    const BandP P = band_args(v, xu, update, factor, info, keep);
+    return visit<int>(v.model, DQP_ERR_BAD_ARG, [&](auto model) {
+        return run_newton_layout<typename decltype(model)::Map>(P, v.stream);
     });
 }
 
@@ -152,8 +146,7 @@ dqp_al_banded_newton_step(const dqp_al_mpc_dims *d, int dyn_id, double dt, const
                           int32_t *info, void *stream)
 {
     const dqp_al_bounds bd = {u_lower, u_upper, 0, 0};
-    return dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, &bd, update, factor, info, stream,
-                                                  1);
+    return dqp_al_banded_newton_step_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, &bd, update, factor, info, stream);
 }
 
 __attribute__((visibility("default"))) int
@@ -161,8 +154,10 @@ dqp_al_banded_newton_step_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt
                                  const double *Qdiag, const double *q, const double *lam, const double *rho,
                                  const dqp_al_bounds *bounds, double *update, void *factor, int32_t *info, void *stream)
 {
-    return dqp::al_banded_newton_step_keep_bounds(d, dyn_id, dt, xu, x0, Qdiag, q, lam, rho, bounds, update, factor, info,
-                                                  stream, 1);
+    // unlike the other `_bounds` entries this one checks its model in front of the nbatch == 0 return (dqp_al_host.h)
+    if (dqp::al_bounds_check(d, bounds) || !model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
+    const dqp::AlProblem v = dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam, rho, bounds, nullptr, stream);
+    return dqp::al_banded_newton_step(v, xu, update, factor, info, true);
 }
 
 // The step with a state box (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per problem
@@ -172,10 +167,9 @@ dqp_al_banded_newton_step_xbounds(const dqp_al_mpc_dims *d, int model, double dt
                                   const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds, double *update, void *factor,
                                   int32_t *info, void *stream)
 {
-    const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl));
-    if (rc) return rc;
-    return dqp::al_banded_newton_step_keep_bounds(d, model, dt, xu, x0, Qdiag, q, lam, rho, bounds, update, factor, info,
-                                                  stream, 1, xbounds);
+    if (const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && model_matches(model, d->n_state, d->n_ctrl))) return rc;
+    const dqp::AlProblem v = dqp::al_problem(d, model, dt, x0, Qdiag, q, lam, rho, bounds, xbounds, stream);
+    return dqp::al_banded_newton_step(v, xu, update, factor, info, true);
 }
 
 __attribute__((visibility("default"))) int
@@ -199,6 +193,21 @@ dqp_al_banded_solve(const dqp_al_mpc_dims *d, int dyn_id, const void *factor, co
     });
 }
 
+// The two caller-linearised steps behind their front checks (the pair has a kernel): the empty batch, the buffers, the launch
+// at the pair -- with a state box in the objects of dqp_al_banded_box.hip / dqp_al_banded_wide.hip
+static int given_step(const dqp::AlProblem &v, const double *xu, const double *x_next, const double *Jx, const double *Ju,
+                      double *update, void *factor, int32_t *info)
+{
+    if (const int r = v.ready(xu && x_next && Jx && Ju && update && factor); r != 1) return r;
+    BandP P = band_args(v, xu, update, factor, info, true);
+    P.xnext = x_next; P.Jx = Jx; P.Ju = Ju;
+    if (v.has_x) return (given_wide(v.n, v.m) ? dqp::al_banded_wide_box_newton : dqp::al_banded_box_newton)(v.n, v.m, P, v.stream);
+    const int rc = visit_pair<BAND_NARROW, int>(v.n, v.m, NOT_NARROW, [&](auto given) {
+        return run_newton_layout<decltype(given)>(P, v.stream);
+    });
+    return rc == NOT_NARROW ? dqp::al_banded_wide_newton(v.n, v.m, P, v.stream) : rc;
+}
+
 /*
  * The same block-tridiagonal Newton step for a dynamics the CALLER linearised (include/dqp.h).
  */
@@ -208,21 +217,11 @@ dqp_al_banded_newton_step_jac_bounds(const dqp_al_mpc_dims *d, const double *xu,
                                      const double *x_next, const double *Jx, const double *Ju, double *update,
                                      void *factor, int32_t *info, void *stream)
 {
-    if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    if (!given_supported(d->n_state, d->n_ctrl) && !given_wide(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    // the wide pairs have the vector instantiation only
-    if (dqp::al_bounds_strided(bounds) && !given_supported(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !x_next || !Jx || !Ju || !update ||
-        !factor)
-        return DQP_ERR_BAD_ARG;
-    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, x_next, Jx, Ju, update, (double *)factor,
-               info, 0.0, d->nbatch, d->T, 1, (long long)bounds->stride_b, (long long)bounds->stride_t};
-    const int rc = visit_pair<BAND_NARROW, int>(d->n_state, d->n_ctrl, NOT_NARROW, [&](auto given) {
-        return run_newton_layout<decltype(given)>(P, stream);
-    });
-    return rc == NOT_NARROW ? dqp::al_banded_wide_newton(d->n_state, d->n_ctrl, P, stream) : rc;
+    if (dqp::al_bounds_check(d, bounds)) return DQP_ERR_BAD_ARG;
+    const dqp::AlProblem v = dqp::al_problem(d, 0, 0.0, x0, Qdiag, q, lam, rho, bounds, nullptr, stream);
+    // the pair in front of the nbatch == 0 return; the wide pairs have the vector instantiation only
+    if (!given_supported(v.n, v.m) && (!given_wide(v.n, v.m) || v.strided())) return DQP_ERR_TOO_LARGE;
+    return given_step(v, xu, x_next, Jx, Ju, update, factor, info);
 }
 
 // The step for caller-linearised dynamics with a state box (include/dqp.h): lam has dqp_al_ncon_xbounds(dims) rows per
@@ -233,20 +232,11 @@ dqp_al_banded_newton_step_jac_xbounds(const dqp_al_mpc_dims *d, const double *xu
                                       const dqp_al_bounds *xbounds, const double *x_next, const double *Jx,
                                       const double *Ju, double *update, void *factor, int32_t *info, void *stream)
 {
-    if (!d || d->nbatch < 0 || d->T < 2 || d->n_state < 1 || d->n_ctrl < 1) return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK || dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK)
-        return DQP_ERR_BAD_ARG;
-    const bool wide = given_wide(d->n_state, d->n_ctrl);
-    if (!wide && !given_supported(d->n_state, d->n_ctrl)) return DQP_ERR_TOO_LARGE;
-    if (d->nbatch == 0) return DQP_OK;
-    if (!xu || !x0 || !Qdiag || !q || !lam || !rho || !bounds->lower || !bounds->upper || !xbounds->lower ||
-        !xbounds->upper || !x_next || !Jx || !Ju || !update || !factor)
-        return DQP_ERR_BAD_ARG;
-    BandP P = {xu, x0, Qdiag, q, lam, rho, bounds->lower, bounds->upper, nullptr, x_next, Jx, Ju, update, (double *)factor,
-               info, 0.0, d->nbatch, d->T, 1, (long long)bounds->stride_b, (long long)bounds->stride_t,
-               xbounds->lower, xbounds->upper, (long long)xbounds->stride_b, (long long)xbounds->stride_t};
-    return wide ? dqp::al_banded_wide_box_newton(d->n_state, d->n_ctrl, P, stream)
-                : dqp::al_banded_box_newton(d->n_state, d->n_ctrl, P, stream);
+    // no model: the sizes and both layouts, then the pair (not al_xbounds_check, whose limit is the registered models')
+    if (dqp::al_bounds_check(d, bounds) || dqp::al_box_layout(xbounds, d, d->n_state)) return DQP_ERR_BAD_ARG;
+    const dqp::AlProblem v = dqp::al_problem(d, 0, 0.0, x0, Qdiag, q, lam, rho, bounds, xbounds, stream);
+    if (!given_wide(v.n, v.m) && !given_supported(v.n, v.m)) return DQP_ERR_TOO_LARGE;
+    return given_step(v, xu, x_next, Jx, Ju, update, factor, info);
 }
 
 __attribute__((visibility("default"))) int

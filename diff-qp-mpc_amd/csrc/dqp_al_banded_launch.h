@@ -28,15 +28,15 @@ template <class Map> int run_newton(const BandP &P, void *stream)
                 const size_t bytes = (size_t)P.T * (C::ROW + 1) * 8 * C::NT * sizeof(double);
                 if (bytes <= 34 * 1024) {
                     DQP_LAUNCH((al_banded_newton_kernel<Map, 8, true>), dim3((P.B + 7) / 8), dim3(64), bytes, (hipStream_t)stream, P BAND_STAMP_ARG);
-                    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+                    return dqp::launched();
                 }
             }
             DQP_LAUNCH((al_banded_newton_kernel<Map, 8>), dim3((P.B + 7) / 8), dim3(64), 0, (hipStream_t)stream, P BAND_STAMP_ARG);
-            return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+            return dqp::launched();
         }
     }
     DQP_LAUNCH((al_banded_newton_kernel<Map, 16>), dim3((P.B + 3) / 4), dim3(64), 0, (hipStream_t)stream, P BAND_STAMP_ARG);
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return dqp::launched();
 }
 
 }  // namespace

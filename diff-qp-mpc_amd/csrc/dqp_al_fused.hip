@@ -452,7 +452,7 @@ template <class Model> int launch_fused(const FusedPS &P, size_t lds, hipStream_
         DQP_LAUNCH(al_solve_fused_kernel<StridedBounds<Model>>, dim3((unsigned)P.B), dim3(64), lds, st, P);
     else
         DQP_LAUNCH(al_solve_fused_kernel<Model>, dim3((unsigned)P.B), dim3(64), lds, st, static_cast<const FusedP &>(P));
-    return hipGetLastError() == hipSuccess ? DQP_OK : DQP_ERR_LAUNCH;
+    return dqp::launched();
 }
 
 }  // namespace
@@ -517,30 +517,24 @@ dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, i
                               double *xu, double *hist_cost, double *hist_lam, double *hist_rho, double *res_norm,
                               double *factor, double *status, int32_t *fail, void *workspace, void *stream)
 {
-    using namespace dqp::dyn;
-    if (!d || d->nbatch < 0 || d->n_state <= 0 || d->n_ctrl <= 0 || d->T < 2 || al_iter < 1 || al_iter > 256 || newton_steps < 1 ||
-        n_prev < 0)
-        return DQP_ERR_BAD_ARG;
-    if (dqp::al_bounds_layout(bounds, d) != DQP_OK) return DQP_ERR_BAD_ARG;
-    const double *u_lower = bounds->lower, *u_upper = bounds->upper;
-    const bool strided = dqp::al_bounds_strided(bounds);
-    if (d->nbatch == 0) return DQP_OK;
-    if (!x_init || !u_init || !x0 || !Qdiag || !q || !u_lower || !u_upper || !lam_in || !rho_in || !xu || !hist_cost ||
-        !hist_lam || !hist_rho || !res_norm || !factor || !fail || !workspace)
-        return DQP_ERR_BAD_ARG;
-    if (n_prev > 0 && (!prev_cost || !prev_lam || !prev_rho)) return DQP_ERR_BAD_ARG;
-    if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl)) return DQP_ERR_BAD_ARG;
-    if (!fused_ok(d, dyn_id, strided)) return DQP_ERR_TOO_LARGE;
-    hipStream_t st = (hipStream_t)stream;
+    const dqp::AlMpcIo io = {al_iter, newton_steps, x_init, u_init, prev_cost, prev_lam, prev_rho, n_prev,
+                             xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, workspace};
+    if (dqp::al_bounds_check(d, bounds) || !io.scalars_ok()) return DQP_ERR_BAD_ARG;
+    const dqp::AlProblem v = dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam_in, rho_in, bounds, nullptr, stream);
+    if (const int r = v.ready(io.buffers_set() && v.model_ok()); r != 1) return r;
+    if (!fused_ok(d, dyn_id, v.strided())) return DQP_ERR_TOO_LARGE;
     // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
-    if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, st) != hipSuccess) return DQP_ERR_LAUNCH;
-    const FusedPS P = {{x_init, u_init, x0, Qdiag, q, u_lower, u_upper, lam_in, rho_in, prev_cost, prev_lam, prev_rho,
-                        xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, dt, d->nbatch, d->T, al_iter,
-                        newton_steps, n_prev}, (long long)bounds->stride_b, (long long)bounds->stride_t};
-    const size_t lds = fused_lds(dyn_id, d->T, strided);
-    return visit<int>(dyn_id, DQP_ERR_TOO_LARGE, [&](auto model) -> int {
+    if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
+    FusedPS P = {};
+    P.x_init = io.x_init; P.u_init = io.u_init; P.x0 = v.x0; P.Qd = v.Qd; P.q = v.q; P.ul = v.u.lower; P.uu = v.u.upper;
+    P.lam_in = v.lam; P.rho_in = v.rho; P.prev_cost = io.prev_cost; P.prev_lam = io.prev_lam; P.prev_rho = io.prev_rho;
+    P.xu = io.xu; P.hist_cost = io.hist_cost; P.hist_lam = io.hist_lam; P.hist_rho = io.hist_rho; P.res_norm = io.res_norm;
+    P.fac = io.factor; P.status = io.status; P.fail = io.fail; P.bsb = v.u.stride_b; P.bst = v.u.stride_t;
+    P.dt = v.dt; P.B = v.B; P.T = v.T; P.al_iter = io.al_iter; P.newton_steps = io.newton_steps; P.n_prev = io.n_prev;
+    const size_t lds = fused_lds(dyn_id, v.T, v.strided());
+    return dqp::dyn::visit<int>(dyn_id, DQP_ERR_TOO_LARGE, [&](auto model) -> int {
         using Map = typename decltype(model)::Map;
-        if constexpr (Map::NX + Map::NU <= FG) return launch_fused<Map>(P, lds, st);
+        if constexpr (Map::NX + Map::NU <= FG) return launch_fused<Map>(P, lds, v.stream);
         else return DQP_ERR_TOO_LARGE;
     });
 }

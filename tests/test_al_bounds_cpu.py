@@ -142,24 +142,101 @@ def test_fused_queries_account_for_the_staged_bounds(robot, lib):
         assert lib.dqp_al_mpc_solve_fused_supported_bounds(ctypes.byref(d), rid, None) == 0
 
 
-def _call_twins(lib, d, rid, bd, given=False):
+def _call_twins(lib, d, rid, bd, given=False, n_steps=4, banded=1, al_iter=2, newton_steps=4, n_prev=0, ncand=20):
     """every launching twin with null buffers -> {name: return code}; nothing is launched at nbatch == 0 or null buffers"""
     r = ctypes.byref
     N = None
     out = {
-        "merit": lib.dqp_al_merit_bounds(r(d), 20, N, N, N, N, N, N, N, bd, N, N),
-        "newton_solve": lib.dqp_al_newton_solve_bounds(r(d), rid, 0.05, 4, 1, N, N, N, N, N, bd, N, N, N, N, N, N),
+        "merit": lib.dqp_al_merit_bounds(r(d), ncand, N, N, N, N, N, N, N, bd, N, N),
+        "newton_solve": lib.dqp_al_newton_solve_bounds(r(d), rid, 0.05, n_steps, banded, N, N, N, N, N, bd, N, N, N, N, N, N),
         "outer_update": lib.dqp_al_outer_update_bounds(r(d), rid, 0.05, N, N, N, N, N, N, bd, N, N, N, N),
-        "mpc_solve": lib.dqp_al_mpc_solve_bounds(r(d), rid, 0.05, 2, 4, N, N, N, N, N, bd, N, N, N, N, N, 0,
-                                                 N, N, N, N, N, N, N, N, N, N),
-        "mpc_solve_fused": lib.dqp_al_mpc_solve_fused_bounds(r(d), rid, 0.05, 2, 4, N, N, N, N, N, bd, N, N, N, N, N, 0,
-                                                             N, N, N, N, N, N, N, N, N, N),
+        "mpc_solve": lib.dqp_al_mpc_solve_bounds(r(d), rid, 0.05, al_iter, newton_steps, N, N, N, N, N, bd, N, N, N, N, N,
+                                                 n_prev, N, N, N, N, N, N, N, N, N, N),
+        "mpc_solve_fused": lib.dqp_al_mpc_solve_fused_bounds(r(d), rid, 0.05, al_iter, newton_steps, N, N, N, N, N, bd, N, N,
+                                                             N, N, N, n_prev, N, N, N, N, N, N, N, N, N, N),
         "banded_newton_step": lib.dqp_al_banded_newton_step_bounds(r(d), rid, 0.05, N, N, N, N, N, N, bd, N, N, N, N),
     }
     if given:
         out["banded_newton_step_jac"] = lib.dqp_al_banded_newton_step_jac_bounds(r(d), N, N, N, N, N, N, bd, N, N, N, N, N,
                                                                                  N, N)
     return out
+
+
+def _call_legacy(lib, d, rid, n_steps=4, banded=1, al_iter=2, newton_steps=4, n_prev=0, ncand=20):
+    """the same through the vector entry points (u_lower / u_upper null as every other buffer)"""
+    r = ctypes.byref
+    N = None
+    return {
+        "merit": lib.dqp_al_merit(r(d), ncand, N, N, N, N, N, N, N, N, N, N, N),
+        "newton_solve": lib.dqp_al_newton_solve(r(d), rid, 0.05, n_steps, banded, N, N, N, N, N, N, N, N, N, N, N, N, N),
+        "outer_update": lib.dqp_al_outer_update(r(d), rid, 0.05, N, N, N, N, N, N, N, N, N, N, N, N),
+        "mpc_solve": lib.dqp_al_mpc_solve(r(d), rid, 0.05, al_iter, newton_steps, N, N, N, N, N, N, N, N, N, N, N, N, n_prev,
+                                          N, N, N, N, N, N, N, N, N, N),
+        "mpc_solve_fused": lib.dqp_al_mpc_solve_fused(r(d), rid, 0.05, al_iter, newton_steps, N, N, N, N, N, N, N, N, N, N, N,
+                                                      N, n_prev, N, N, N, N, N, N, N, N, N, N),
+        "banded_newton_step": lib.dqp_al_banded_newton_step(r(d), rid, 0.05, N, N, N, N, N, N, N, N, N, N, N, N),
+        "banded_newton_step_jac": lib.dqp_al_banded_newton_step_jac(r(d), N, N, N, N, N, N, N, N, N, N, N, N, N, N, N),
+    }
+
+
+# Two faults at once, at the vector layout (0, 0) with every buffer null: which one an entry reports.  A row is
+# (nbatch, (n_state, n_ctrl, T), model, scalar arguments, {entry: return code where it is not the row's default}); the
+# default is DQP_OK at nbatch == 0 -- an empty batch returns in front of the model, the kernels' limits and the pointers --
+# and DQP_ERR_BAD_ARG at nbatch == 3 (the null buffers, or the model in front of them).  The exceptions: the banded step
+# checks its model in front of the nbatch == 0 return, the caller-linearised step its pair (DQP_ERR_TOO_LARGE); the scalar
+# arguments are checked with the sizes, in front of everything.
+UNREGISTERED, CARTPOLE1L, REXQUADROTOR = 99, 2, 6
+PRECEDENCE_ROWS = [
+    # an unregistered model id, at a compiled pair
+    (0, (4, 1, 6), UNREGISTERED, {}, {"banded_newton_step": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), 0, {}, {"banded_newton_step": DQP_ERR_BAD_ARG}),
+    (3, (4, 1, 6), UNREGISTERED, {}, {}),
+    (3, (4, 1, 6), 0, {}, {}),
+    # sizes beyond the block-tridiagonal kernels (no registered model has them: the model check meets them first)
+    (0, (13, 4, 6), REXQUADROTOR, {}, {"banded_newton_step": DQP_ERR_BAD_ARG}),
+    (0, (16, 1, 6), REXQUADROTOR, {}, {"banded_newton_step": DQP_ERR_BAD_ARG, "banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (0, (13, 4, 6), UNREGISTERED, {}, {"banded_newton_step": DQP_ERR_BAD_ARG}),
+    (0, (16, 1, 6), UNREGISTERED, {}, {"banded_newton_step": DQP_ERR_BAD_ARG, "banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (3, (13, 4, 6), REXQUADROTOR, {}, {}),
+    (3, (16, 1, 6), REXQUADROTOR, {}, {"banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (3, (13, 4, 6), UNREGISTERED, {}, {}),
+    (3, (16, 1, 6), UNREGISTERED, {}, {"banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    # dqp_al_newton_solve_bounds with banded = 0: sizes beyond the dense kernel, T (n + m) > 128
+    (0, (9, 1, 6), REXQUADROTOR, {"banded": 0}, {"banded_newton_step": DQP_ERR_BAD_ARG, "banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (0, (4, 3, 6), CARTPOLE1L, {"banded": 0}, {"banded_newton_step": DQP_ERR_BAD_ARG, "banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (0, (12, 4, 6), REXQUADROTOR, {"banded": 0}, {}),
+    (0, (4, 1, 26), CARTPOLE1L, {"banded": 0}, {}),
+    (3, (9, 1, 6), REXQUADROTOR, {"banded": 0}, {"banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (3, (4, 3, 6), CARTPOLE1L, {"banded": 0}, {"banded_newton_step_jac": DQP_ERR_TOO_LARGE}),
+    (3, (12, 4, 6), REXQUADROTOR, {"banded": 0}, {}),
+    (3, (4, 1, 26), CARTPOLE1L, {"banded": 0}, {}),
+    # scalar arguments: in front of the nbatch == 0 return
+    (0, (4, 1, 6), CARTPOLE1L, {"n_steps": 0}, {"newton_solve": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"n_steps": 0, "banded": 0}, {"newton_solve": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"al_iter": 0}, {"mpc_solve": DQP_ERR_BAD_ARG, "mpc_solve_fused": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"al_iter": 257}, {"mpc_solve": DQP_ERR_BAD_ARG, "mpc_solve_fused": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"al_iter": 256}, {}),
+    (0, (4, 1, 6), CARTPOLE1L, {"newton_steps": 0}, {"mpc_solve": DQP_ERR_BAD_ARG, "mpc_solve_fused": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"n_prev": -1}, {"mpc_solve": DQP_ERR_BAD_ARG, "mpc_solve_fused": DQP_ERR_BAD_ARG}),
+    (0, (4, 1, 6), CARTPOLE1L, {"ncand": -1}, {"merit": DQP_ERR_BAD_ARG}),
+    # ... and in front of an unregistered model and of sizes beyond the kernels
+    (0, (13, 4, 6), UNREGISTERED, {"n_steps": 0, "al_iter": 257, "ncand": -1},
+     {"newton_solve": DQP_ERR_BAD_ARG, "mpc_solve": DQP_ERR_BAD_ARG, "mpc_solve_fused": DQP_ERR_BAD_ARG,
+      "merit": DQP_ERR_BAD_ARG, "banded_newton_step": DQP_ERR_BAD_ARG}),
+    (3, (4, 1, 6), CARTPOLE1L, {"n_steps": 0, "al_iter": 0, "n_prev": -1, "ncand": -1}, {}),
+]
+
+
+def _precedence_rows():
+    """-> (row, dims, scalar arguments, {entry: expected code}) of PRECEDENCE_ROWS"""
+    from diff_qp_mpc_amd import _lib
+    names = ("merit", "newton_solve", "outer_update", "mpc_solve", "mpc_solve_fused", "banded_newton_step",
+             "banded_newton_step_jac")
+    for row in PRECEDENCE_ROWS:
+        B, (n, m, T), rid, scalars, exceptions = row
+        want = dict.fromkeys(names, 0 if B == 0 else DQP_ERR_BAD_ARG)
+        want.update(exceptions)
+        yield row, _lib.dqp_al_mpc_dims(B, n, m, T), rid, scalars, want
 
 
 def test_every_twin_checks_the_layout(lib):
@@ -186,6 +263,12 @@ def test_every_twin_checks_the_layout(lib):
             nul = _lib.dqp_al_bounds(None, None, sb, st)
             for name, rc in _call_twins(lib, d, rid, ctypes.byref(nul), given=True).items():
                 assert rc == (0 if B == 0 else DQP_ERR_BAD_ARG), (name, B, sb, st, rc)
+    # two faults at once (PRECEDENCE_ROWS), at the vector layout with null lower / upper
+    assert (_lib.DQP_DYN["cartpole1l"], _lib.DQP_DYN["rexquadrotor"]) == (CARTPOLE1L, REXQUADROTOR)
+    assert UNREGISTERED not in _lib.DQP_DYN.values() and 0 not in _lib.DQP_DYN.values()
+    vec = _lib.dqp_al_bounds(None, None, 0, 0)
+    for row, d, rid, scalars, want in _precedence_rows():
+        assert _call_twins(lib, d, rid, ctypes.byref(vec), given=True, **scalars) == want, row
     # the wide pairs (DQP_BAND_WIDE_SIZES) have the vector instantiation only: DQP_ERR_TOO_LARGE at non-zero strides
     d = _lib.dqp_al_mpc_dims(0, 13, 4, 6)
     N = None
@@ -211,6 +294,9 @@ def test_old_entry_points_keep_their_answers(lib):
                                     N) == want
         assert lib.dqp_al_mpc_solve_fused(d, rid, 0.05, 2, 4, N, N, N, N, N, N, N, N, N, N, N, N, 0, N, N, N, N, N, N, N, N,
                                           N, N) == want
+    # every row of PRECEDENCE_ROWS: the answer of the `_bounds` twin at strides (0, 0)
+    for row, d, rid, scalars, want in _precedence_rows():
+        assert _call_legacy(lib, d, rid, **scalars) == want, row
 
 
 # ------------------------------------------------------------------ the oracle under (B, T, m) bounds

@@ -61,18 +61,25 @@ def test_ncon_and_bytes_queries(lib):
     assert lib.dqp_al_ncon_xbounds(None) == 0
 
 
-def _call_all(lib, d, rid, bd, xbd):
+def _call_all(lib, d, rid, bd, xbd, n_steps=4, al_iter=2, newton_steps=4, n_prev=0):
     """every new launching entry with null buffers -> {name: return code}; nothing is launched at nbatch == 0 or with
     null buffers"""
     r = ctypes.byref
     N = None
     return {
         "banded_newton_step": lib.dqp_al_banded_newton_step_xbounds(r(d), rid, 0.05, N, N, N, N, N, N, bd, xbd, N, N, N, N),
-        "newton_solve": lib.dqp_al_newton_solve_xbounds(r(d), rid, 0.05, 4, N, N, N, N, N, bd, xbd, N, N, N, N, N, N),
+        "newton_solve": lib.dqp_al_newton_solve_xbounds(r(d), rid, 0.05, n_steps, N, N, N, N, N, bd, xbd, N, N, N, N, N, N),
         "outer_update": lib.dqp_al_outer_update_xbounds(r(d), rid, 0.05, N, N, N, N, N, N, bd, xbd, N, N, N, N),
-        "mpc_solve": lib.dqp_al_mpc_solve_xbounds(r(d), rid, 0.05, 2, 4, N, N, N, N, N, bd, xbd, N, N, N, N, N, 0,
-                                                  N, N, N, N, N, N, N, N, N, N),
+        "mpc_solve": lib.dqp_al_mpc_solve_xbounds(r(d), rid, 0.05, al_iter, newton_steps, N, N, N, N, N, bd, xbd, N, N, N, N,
+                                                  N, n_prev, N, N, N, N, N, N, N, N, N, N),
     }
+
+
+# scalar argument faults of the `_xbounds` entries: behind al_xbounds_check (so behind DQP_ERR_TOO_LARGE), in front of the
+# nbatch == 0 return.  (scalar arguments, the entries that then return DQP_ERR_BAD_ARG at sizes a model has)
+SCALAR_FAULTS = [({"n_steps": 0}, ("newton_solve",)), ({"al_iter": 0}, ("mpc_solve",)), ({"al_iter": 257}, ("mpc_solve",)),
+                 ({"newton_steps": 0}, ("mpc_solve",)), ({"n_prev": -1}, ("mpc_solve",)),
+                 ({"n_steps": 0, "al_iter": 0}, ("newton_solve", "mpc_solve")), ({"al_iter": 256}, ())]
 
 
 def test_return_code_table(lib):
@@ -96,6 +103,10 @@ def test_return_code_table(lib):
                 # null lower / upper of the state box: behind the nbatch == 0 return
                 for name, rc in _call_all(lib, d, rid, r(ok_u), r(box(n, sb, st, None))).items():
                     assert rc == (0 if B == 0 else DQP_ERR_BAD_ARG), (robot, name, B, sb, st, rc)
+            for scalars, refused in SCALAR_FAULTS:
+                for name, rc in _call_all(lib, d, rid, r(ok_u), r(box(n)), **scalars).items():
+                    want = DQP_ERR_BAD_ARG if (name in refused or B > 0) else 0
+                    assert rc == want, (robot, name, B, scalars, rc)
             # a null or bad-stride state box, a null or bad-stride control box: in front of it
             for name, rc in _call_all(lib, d, rid, r(ok_u), None).items():
                 assert rc == DQP_ERR_BAD_ARG, (robot, name, B, rc)
@@ -122,6 +133,17 @@ def test_return_code_table(lib):
             for rid in (0, _lib.DQP_DYN["rexquadrotor"]):
                 for name, rc in _call_all(lib, d, rid, r(box(m)), r(box(n))).items():
                     assert rc == DQP_ERR_TOO_LARGE, (name, B, n, m, rid, rc)
+                # two faults at once: illegal strides of either box are reported in front of the sizes' limit, and the
+                # limit in front of the model (the rows above: no model has these sizes)
+                for name, rc in _call_all(lib, d, rid, r(box(m)), r(box(n, n + 1, 0))).items():
+                    assert rc == DQP_ERR_BAD_ARG, (name, B, n, m, rid, rc)
+                for name, rc in _call_all(lib, d, rid, r(box(m, 0, m + 1)), r(box(n))).items():
+                    assert rc == DQP_ERR_BAD_ARG, (name, B, n, m, rid, rc)
+            for name, rc in _call_all(lib, d, 99, r(box(m)), r(box(n))).items():
+                assert rc == DQP_ERR_TOO_LARGE, (name, B, n, m, rc)
+            for scalars, _ in SCALAR_FAULTS:        # the limit in front of the scalar arguments
+                for name, rc in _call_all(lib, d, _lib.DQP_DYN["rexquadrotor"], r(box(m)), r(box(n)), **scalars).items():
+                    assert rc == DQP_ERR_TOO_LARGE, (name, B, n, m, scalars, rc)
         # the sizes and horizon checks of the twins
         for n, m, Tb in ((0, 1, T), (2, 0, T), (2, 1, 1)):
             d = _lib.dqp_al_mpc_dims(B, n, m, Tb)

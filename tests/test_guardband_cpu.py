@@ -195,7 +195,7 @@ def test_run_guarded_passes_clean_code_and_catches_the_three_faults():
 
 def test_newton_solve_bytes_is_exactly_the_carve():
     """dqp_al_newton_solve_bytes: per problem the update (nz), 20 candidate merits, the current merit and one double's
-    room for the int32 pivot flag -- the carve of newton_solve_impl (csrc/dqp_al.hip), without the two doubles of slack
+    room for the int32 pivot flag -- the carve of newton_work (csrc/dqp_al.hip), without the two doubles of slack
     earlier versions added -- and the dense form's arrays in front of the same tail; the other AL workspace sizes are
     this one (include/dqp.h).  Host functions: no GPU."""
     import ctypes
