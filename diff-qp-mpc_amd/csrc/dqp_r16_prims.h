@@ -151,20 +151,6 @@ __device__ __forceinline__ double frsqrt(double d)
     } while (0)
 #endif
 
-#if defined(DQP_STAMPS_C)     /* experiment: the 16 slots record the reflector loop of the null-space setup */
-#undef STAMP
-#define STAMP(P, i) do { } while (0)
-#define STAMPC(P, i)                                                                 \
-    do {                                                                             \
-        if ((P).stamps) {                                                            \
-            __builtin_amdgcn_sched_barrier(0);                                       \
-            const unsigned long long t__ = __builtin_readcyclecounter();             \
-            if (threadIdx.x == 0) (P).stamps[blockIdx.x * 16 + (i)] = t__;           \
-            __builtin_amdgcn_sched_barrier(0);                                       \
-        }                                                                            \
-    } while (0)
-#endif
-
 constexpr __host__ __device__ int slots(int n) { return (n + 15) / 16; }
 constexpr __host__ __device__ int tri(int i) { return i * (i + 1) / 2; }
 
@@ -276,14 +262,9 @@ __device__ __forceinline__ bool chol_rows(double (&L)[S][N], double (&rd)[S], in
     return ok;
 }
 
-// Build-time A/B switches of the factorisation (both default on; -DDQP_LU_LOOKAHEAD=0 / -DDQP_LU_FOLD_RHS=0
-// give the plain forms, bit-identical in their results).
-#ifndef DQP_LU_LOOKAHEAD
-#define DQP_LU_LOOKAHEAD 1
-#endif
-#ifndef DQP_LU_FOLD_RHS
-#define DQP_LU_FOLD_RHS 1
-#endif
+// The factorisation below has one form: the look-ahead pivot chain and the folded right-hand side both won their
+// measurements against the plain order, with bit-identical results.  Timing a further variant needs
+// no switch in this file: tools/ab_variants.py builds one from a source file kept outside the tree.
 
 // ties the scheduling of two independent values together: whatever consumes the outputs comes after
 // everything that produced either input (the look-ahead pivot chain is spread over the trailing
@@ -293,7 +274,7 @@ __device__ __forceinline__ bool chol_rows(double (&L)[S][N], double (&rd)[S], in
 // Unpivoted LU of the row-distributed matrix (in place: unit-lower multipliers below the
 // diagonal, U on/above).  rdu[s] = 1/U[i][i].
 //
-// Look-ahead (LA): step k updates column k+1 first and takes the next pivot's reciprocal from it --
+// Look-ahead: step k updates column k+1 first and takes the next pivot's reciprocal from it --
 // broadcast, v_rcp_f64 and the four refinement FMAs of frcp, one link after each of the following
 // column updates -- so the chain's latency and the DPP-after-VALU wait states hide under the rest
 // of the trailing update instead of standing in front of step k+1.  Same operations on the same
@@ -303,17 +284,15 @@ __device__ __forceinline__ bool chol_rows(double (&L)[S][N], double (&rd)[S], in
 // with lu_solve's own expressions and masks: at step k < N-1, b[s] = fma(-L[s][k], bcast(b[k]), b[s]).
 // For a right-hand side known before the factorisation this takes the sweep's N-1 dependent
 // broadcast+FMA links off the critical path; lu_solve_U finishes the solve.
-template <int S, int N, bool RHS, bool LA>
+template <int S, int N, bool RHS>
 __device__ __forceinline__ void lu_rows_impl(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
 {
 #pragma unroll
     for (int s = 0; s < S; ++s) rdu[s] = 0.0;
-    double rp = 0.0;
-    if (LA) rp = frcp(rb(T[0][0], 0));
+    double rp = frcp(rb(T[0][0], 0));
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const int sk = k >> 4, lk = k & 15;
-        if (!LA) rp = frcp(rb(T[sk][k], lk));
         if (r == lk) rdu[sk] = rp;
         PIN(rdu[sk]);
         double l[S];
@@ -341,7 +320,7 @@ __device__ __forceinline__ void lu_rows_impl(double (&T)[S][N], double (&rdu)[S]
                     else b[s] = fma(-mask_hi(T[s][k], r > lk), bk, b[s]);
                 }
             }
-            if (LA && j >= k + 2 && stage < 6) {       // one link per column from k+2 on
+            if (j >= k + 2 && stage < 6) {             // one link per column from k+2 on
                 double &tj = T[S - 1][j];              // (a slot that every step still updates)
                 if (stage == 0) { PIN2(tj, T[(k + 1) >> 4][k + 1]); pd = rb(T[(k + 1) >> 4][k + 1], (k + 1) & 15); }
                 else if (stage == 1) { PIN2(tj, pd); pr = __builtin_amdgcn_rcp(pd); }
@@ -350,7 +329,7 @@ __device__ __forceinline__ void lu_rows_impl(double (&T)[S][N], double (&rdu)[S]
                 ++stage;
             }
         }
-        if (LA && k + 1 < N) {                         // what the remaining columns were too few for
+        if (k + 1 < N) {                               // what the remaining columns were too few for
             if (stage == 0) { pd = rb(T[(k + 1) >> 4][k + 1], (k + 1) & 15); ++stage; }
             if (stage == 1) { pr = __builtin_amdgcn_rcp(pd); ++stage; }
 #pragma unroll
@@ -369,7 +348,7 @@ __device__ __forceinline__ void lu_rows(double (&T)[S][N], double (&rdu)[S], int
     double none[S];            // lu_rows_impl<RHS = false> never touches b: dead after inlining
 #pragma unroll
     for (int s = 0; s < S; ++s) none[s] = 0.0;
-    lu_rows_impl<S, N, false, DQP_LU_LOOKAHEAD != 0>(T, rdu, none, r);
+    lu_rows_impl<S, N, false>(T, rdu, none, r);
 }
 
 // b <- U^-1 y: the U sweep and the final scaling of lu_solve.  A lane keeps its own y_k unscaled (the
@@ -417,21 +396,16 @@ __device__ __forceinline__ void lu_solve(const double (&T)[S][N], const double (
 template <int S, int N>
 __device__ __forceinline__ void lu_rows_rhs(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
 {
-    lu_rows_impl<S, N, true, DQP_LU_LOOKAHEAD != 0>(T, rdu, b, r);
+    lu_rows_impl<S, N, true>(T, rdu, b, r);
 }
 
-// factor + solve for a right-hand side known before the factorisation: b <- T^-1 b.  The callers pass
-// FOLD = (DQP_LU_FOLD_RHS != 0); false is the plain pair lu_rows + lu_solve.
-template <int S, int N, bool FOLD>
+// factor + solve for a right-hand side known before the factorisation: b <- T^-1 b, the L sweep folded into
+// the factorisation (the same values as the pair lu_rows + lu_solve)
+template <int S, int N>
 __device__ __forceinline__ void lu_factor_solve(double (&T)[S][N], double (&rdu)[S], double (&b)[S], int r)
 {
-    if (FOLD) {
-        lu_rows_rhs<S, N>(T, rdu, b, r);
-        lu_solve_U<S, N>(T, rdu, b, r);
-    } else {
-        lu_rows<S, N>(T, rdu, r);
-        lu_solve<S, N>(T, rdu, b, r);
-    }
+    lu_rows_rhs<S, N>(T, rdu, b, r);
+    lu_solve_U<S, N>(T, rdu, b, r);
 }
 
 // b <- L^-1 b, L lower triangular row-distributed in registers (rd = reciprocal diagonal)
@@ -469,22 +443,13 @@ __device__ __forceinline__ void tri_store(double *P, const double (&L)[S][N], in
     }
 }
 
-// Build-time A/B switch of the LDS operand prefetch (default on; -DDQP_LDS_PREFETCH=0 gives the plain forms,
-// bit-identical in their results).  With one wavefront per SIMD nothing else runs while a wave sits in
+// The LDS operand prefetch.  With one wavefront per SIMD nothing else runs while a wave sits in
 // s_waitcnt lgkmcnt for an operand it asked for just in time, so outside the iteration loop the LDS operands
-// of a dependent chain are fetched ahead of it: the triangular solves keep a ring of DQP_TRI_RING columns in
+// of a dependent chain are fetched ahead of it: the triangular solves keep a ring of TRI_RING columns in
 // flight, the reflector chains the next reflector's tail, the row solves of the setup the next 8 entries.
-// The parts can be switched on their own (tools/ab_variants.py): DQP_PF_TRI, DQP_PF_REFLECT, DQP_PF_ROWS,
-// DQP_PF_HEADS.
-#ifndef DQP_LDS_PREFETCH
-#define DQP_LDS_PREFETCH 1
-#endif
-#ifndef DQP_TRI_RING
-#define DQP_TRI_RING 4         /* columns ahead: RING x one step's DPP chain (~18 cycles) > the LDS round trip */
-#endif
-#ifndef DQP_PF_TRI
-#define DQP_PF_TRI DQP_LDS_PREFETCH
-#endif
+// The plain forms (D = 0 below; each entry read where it is used, bit-identical in their results) stay for the
+// sizes whose kernels have no register to hold an operand ahead of its use: a kernel Cfg picks by size (Cfg::PF).
+constexpr int TRI_RING = 4;    /* columns ahead: RING x one step's DPP chain (~18 cycles) > the LDS round trip */
 
 // Orders a prefetch: every LDS read issued above stays above, whatever consumes x comes below (an LDS read
 // is ordered against the "memory" clobber, the arithmetic through x -- a scheduling barrier alone orders
@@ -514,7 +479,7 @@ template <int S> __device__ __forceinline__ void ring_use(double (&c)[S], int k)
 }
 
 // y = L x with L the packed lower triangle in LDS (x, y distributed length N)
-template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
+template <int S, int N, int D = TRI_RING>
 __device__ __forceinline__ void tri_mv(const double *P, const double (&x)[S], double (&y)[S], int r)
 {
 #pragma unroll
@@ -557,7 +522,7 @@ __device__ __forceinline__ void tri_mv(const double *P, const double (&x)[S], do
 }
 
 // b <- L^-1 b with L packed in LDS (forward substitution; rd distributed reciprocal diagonal)
-template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
+template <int S, int N, int D = TRI_RING>
 __device__ __forceinline__ void tri_solve(const double *P, const double (&rd)[S], double (&b)[S], int r)
 {
     if constexpr (D == 0) {
@@ -604,7 +569,7 @@ __device__ __forceinline__ void tri_solve(const double *P, const double (&rd)[S]
 
 // b <- L^-T b with L packed in LDS: x_j = (b_j - sum_{i>j} L[i][j] x_i) / L[j][j]; the sum over
 // rows is a row reduction (the transposed access pattern of row-distributed storage).
-template <int S, int N, int D = (DQP_PF_TRI ? DQP_TRI_RING : 0)>
+template <int S, int N, int D = TRI_RING>
 __device__ __forceinline__ void tri_solve_T(const double *P, const double (&rd)[S], double (&b)[S], int r)
 {
     if constexpr (D == 0) {
@@ -673,47 +638,6 @@ __device__ __forceinline__ void vec_get(const double *P, double (&v)[S], int n, 
 }
 
 // Row-distributed load of an nrows x NC matrix (rows beyond nrows are zero).
-// The same row-distributed load staged through LDS: the 16 lanes of a QP copy the contiguous matrix
-// with 16 bytes per lane -- 256 contiguous bytes per load instruction and QP, instead of 16 rows 8 NC
-// bytes apart (64 distinct cache lines per instruction over the four QPs of a wavefront) -- one register
-// slot (16 rows) at a time, and each lane reads its row back from LDS.  `stage` needs 16 NC doubles.
-// V2: the matrix starts on a 16-byte boundary for every QP (rows x NC even).
-template <int S, int NC, bool V2>
-__device__ __forceinline__ void load_rows_staged(const double *src, int nrows, double (&dst)[S][NC], int r, double *stage)
-{
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int nr = nrows - 16 * s < 16 ? nrows - 16 * s : 16;       // rows of this slot
-        const double *blk = src + 16 * s * NC;
-        if (V2 && (reinterpret_cast<unsigned long long>(blk) & 15ull) == 0) {      // (a view may start on an 8-byte boundary)
-            const double2 *b2 = reinterpret_cast<const double2 *>(blk);
-            double2 *s2 = reinterpret_cast<double2 *>(stage);
-#pragma unroll
-            for (int k = 0; k < (16 * NC / 2 + 15) / 16; ++k) {
-                const int e = r + 16 * k;
-                if (e < nr * NC / 2) s2[e] = b2[e];
-            }
-            if ((nr * NC) & 1) { if (r == 0) stage[nr * NC - 1] = blk[nr * NC - 1]; }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const int e = r + 16 * k;
-                if (e < nr * NC) stage[e] = blk[e];
-            }
-        }
-        __syncthreads();
-        const double *row = stage + (r < nr ? r : 0) * NC;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) dst[s][j] = row[j];
-        if (16 * s + 15 >= nrows) {
-            const double keep = r < nr ? 1.0 : 0.0;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) dst[s][j] *= keep;
-        }
-        __syncthreads();
-    }
-}
-
 template <int S, int NC>
 __device__ __forceinline__ void load_rows(const double *src, int nrows, double (&dst)[S][NC], int r)
 {
@@ -780,7 +704,7 @@ __device__ __forceinline__ void factor_T_rhs(double *lds, double (&T)[C::SM][C::
                                              double (&rdu)[C::SM], double (&b)[C::SM], int r)
 {
     load_T<C>(lds, T, rdiag, dinv, r);
-    lu_factor_solve<C::SM, C::M, DQP_LU_FOLD_RHS != 0>(T, rdu, b, r);
+    lu_factor_solve<C::SM, C::M>(T, rdu, b, r);
 }
 
 }  // namespace r16

@@ -41,48 +41,25 @@ namespace r16n {
 
 using namespace dqp::r16;
 
-// the parts of DQP_LDS_PREFETCH (dqp_r16_prims.h) that live in this file
-#ifndef DQP_PF_REFLECT
-#define DQP_PF_REFLECT DQP_LDS_PREFETCH      /* apply_Qf / apply_QfT: the next reflector's tail */
-#endif
-#ifndef DQP_PF_ROWS
-#define DQP_PF_ROWS DQP_LDS_PREFETCH         /* row-uniform Lq / tail entries of the setup: 8 doubles ahead */
-#endif
-#ifndef DQP_PF_HEADS
-#define DQP_PF_HEADS DQP_LDS_PREFETCH        /* the epilogue's parked iterate: read ahead of the tails' barriers */
-#endif
-
+// Every selection below is made from the problem size.  Each size drops W and U from the register file between the
+// setup and the epilogue (they are dead during the iteration and in the workspace anyway, as the backward context),
+// runs the ordered setup (pin / exec-masked tail stores) and sends the factorisation context to the workspace piece
+// by piece as each piece becomes final, so that its 16 KB per QP drain under the following phases instead of in one
+// burst at the end.
 template <int N_, int M_, int E_> struct Cfg {
     static constexpr int N = N_, M = M_, E = E_, R = N_ - E_;
     static constexpr int SN = slots(N_), SM = slots(M_), SR = slots(N_ - E_);
-    static constexpr int SE = E_ > 0 ? slots(E_) : 1, EC = E_ > 0 ? E_ : 1;
-    static constexpr bool PARK = slots(N_) >= 3;        // W, U leave the registers between setup and epilogue
-    // The three-slot sizes keep the plain forms of DQP_LDS_PREFETCH: their forward kernels have no register to
-    // hold an operand ahead of its use -- each part alone adds scratch there (tools/kernel_resources.py:
-    // (35, 10, 30) 0 -> 44-80 B, (40, 20, 30) 336 -> 524-556 B).
+    static constexpr int SE = E_ > 0 ? slots(E_) : 1;
+    // three register slots per N-space matrix: the setup cannot hold Gh, Ah and a reflector at once
+    static constexpr bool PARK = slots(N_) >= 3;
+    static constexpr bool SPLIT = PARK;                 // A pass (B, C, D on Ah) before the G pass
+    // The LDS operand prefetch (dqp_r16_prims.h): the next reflector's tail in apply_Qf / apply_QfT, the row-uniform
+    // Lq entries of the setup 8 doubles ahead, the epilogue's parked iterate ahead of the tails' barriers, and RING
+    // columns of the triangular solves.  The three-slot sizes keep the plain forms: their forward kernels have no
+    // register to hold an operand ahead of its use -- each part alone adds scratch there
+    // (tools/kernel_resources.py: (35, 10, 30) 0 -> 44-80 B, (40, 20, 30) 336 -> 524-556 B).
     static constexpr bool PF = !PARK;
-    static constexpr int RING = (PF && DQP_PF_TRI) ? DQP_TRI_RING : 0;
-    static constexpr bool PF_REFLECT = PF && DQP_PF_REFLECT, PF_ROWS = PF && DQP_PF_ROWS, PF_HEADS = PF && DQP_PF_HEADS;
-#ifndef DQP_R16N_PARK_WU
-#define DQP_R16N_PARK_WU 1
-#endif
-    // the same for the two-slot sizes, without the split passes: W and U are dead between setup and epilogue and are
-    // in the workspace anyway (the backward context); 1 drops them from the register file during the iteration
-    static constexpr bool PARKWU = PARK || DQP_R16N_PARK_WU;
-#ifndef DQP_R16N_PIN_ALL
-#define DQP_R16N_PIN_ALL 1
-#endif
-    static constexpr bool PIN = PARK || DQP_R16N_PIN_ALL;   // ordered setup (pin / exec-masked tail stores)
-#ifndef DQP_R16N_SPLIT_ALL
-#define DQP_R16N_SPLIT_ALL 0
-#endif
-    static constexpr bool SPLIT = PARK || DQP_R16N_SPLIT_ALL;   // A pass (B, C, D on Ah) before the G pass
-#ifndef DQP_R16N_EARLY_CTX
-#define DQP_R16N_EARLY_CTX 1
-#endif
-    // the factorisation context goes to the workspace piece by piece as each piece becomes final, so
-    // that its 16 KB per QP drain under the following phases instead of in one burst at the end
-    static constexpr bool EARLY = DQP_R16N_EARLY_CTX;
+    static constexpr int RING = PF ? TRI_RING : 0;
     // LDS per QP (doubles)
     static constexpr int tailsz = E_ * (N_ - E_) + E_ * (E_ - 1) / 2;     // sum_k c_k, c_k = R + k
     static constexpr int oLq = 0;                       // packed lower triangle of Lq
@@ -97,14 +74,9 @@ template <int N_, int M_, int E_> struct Cfg {
     static constexpr int oDummy = oBc + 2;              // 16 write-only sink slots
     static constexpr int ldsQP = oDummy + 16;
     static constexpr int ldsQPpad = (ldsQP + 1) & ~1;
-#ifndef DQP_R16N_STAGED
-#define DQP_R16N_STAGED 0
-#endif
-    // Q, G, A through LDS with coalesced 16-byte-per-lane loads (a slot of 16 rows must fit the LDS behind
-    // the packed Lq).  Measured at the metric size, B = 4096: 226.3 us per launch against 217.0 us with each lane
-    // streaming its own row (load_rows) -- the copy, the two LDS hops and their waits cost more than the 4x
-    // fewer cache-line lookups save -- so it stays off; -DDQP_R16N_STAGED=1 builds it.
-    static constexpr bool STAGED = DQP_R16N_STAGED && 16 * N_ <= ldsQP - oTl;
+    // Q, G and A come in with each lane streaming its own row (load_rows).  Staging them through LDS with coalesced
+    // 16-byte-per-lane loads was measured at the metric size, B = 4096: 226.3 us per launch against 217.0 us -- the
+    // copy, the two LDS hops and their waits cost more than the 4x fewer cache-line lookups save.
     __host__ __device__ static constexpr int toff(int k) { return k * (N_ - E_) + k * (k - 1) / 2; }
     // caller workspace per QP (doubles): the reflector tails (parked during the iteration), then
     // the factorisation context the backward pass restarts from -- what the reference keeps on
@@ -254,14 +226,14 @@ template <class C>
 __device__ __forceinline__ void apply_QfT(const double *lds, const double (&tau)[C::SE],
                                           double (&v)[C::SN], int r)
 {
-    reflect_chain<C, C::PF_REFLECT>(lds, tau, v, C::E - 1, -1, r);
+    reflect_chain<C, C::PF>(lds, tau, v, C::E - 1, -1, r);
 }
 // v <- Qf v = H_{E-1} ... H_0 v   (H_0 first)
 template <class C>
 __device__ __forceinline__ void apply_Qf(const double *lds, const double (&tau)[C::SE],
                                          double (&v)[C::SN], int r)
 {
-    reflect_chain<C, C::PF_REFLECT>(lds, tau, v, 0, 1, r);
+    reflect_chain<C, C::PF>(lds, tau, v, 0, 1, r);
 }
 
 // Row-uniform reads of the per-QP LDS array as a stream of 8-double chunks on the array's own 64-byte grid,
@@ -491,8 +463,8 @@ __device__ __forceinline__ void park_GU(double *ws, const State<C> &st, int r)
         }
     }
 }
-// W = Gh[:, R:] and U = Ah[:, R:] back from the workspace (3-slot sizes drop them from the register
-// file between the setup and the epilogue)
+// W = Gh[:, R:] and U = Ah[:, R:] back from the workspace (the setup drops them from the register
+// file; the epilogue needs them again)
 template <class C>
 __device__ __forceinline__ void unpark_WU(const double *ws, State<C> &st, int r)
 {
@@ -602,13 +574,12 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     {   // A: Q -> Lq -> packed LDS
         double Lq[SN][N];
         if (mpc) mpc_rows_Q<SN, N>(P, qp, Lq, r);
-        else if (C::STAGED) load_rows_staged<SN, N, (N * N) % 2 == 0>(P.Q + qp * P.sQ, N, Lq, r, lds + C::oTl);
         else load_rows<SN, N>(P.Q + qp * P.sQ, N, Lq, r);
         if (!chol_rows<SN, N>(Lq, st.rdq, r)) st.status = DQP_STATUS_Q_NOT_PD;
         tri_store<SN, N>(lds + C::oLq, Lq, r, dummy);
     }
     __syncthreads();
-    if (C::EARLY) {
+    {   // Lq and 1/diag(Lq) are final: the first piece of the factorisation context
         double *ws = P.workspace + qp * (long long)C::wsQP;
         lds_to_ctx<tri(N)>(lds + C::oLq, ws + C::wLq, r);
 #pragma unroll
@@ -626,26 +597,21 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
         if (!C::SPLIT) mpc_rows_G<SM, N>(P, M, st.Gh, r);
         if (E > 0) mpc_rows_A<SE, N>(P, qp, E, st.Ah, r);
     } else {
-        if (C::STAGED) {
-            if (!C::SPLIT) load_rows_staged<SM, N, (M * N) % 2 == 0>(P.G + qp * P.sG, M, st.Gh, r, lds + C::oTl);
-            if (E > 0) load_rows_staged<SE, N, (C::EC * N) % 2 == 0>(P.A + qp * P.sA, E, st.Ah, r, lds + C::oTl);
-        } else {
-            if (!C::SPLIT) load_rows<SM, N>(P.G + qp * P.sG, M, st.Gh, r);
-            if (E > 0) load_rows<SE, N>(P.A + qp * P.sA, E, st.Ah, r);
-        }
+        if (!C::SPLIT) load_rows<SM, N>(P.G + qp * P.sG, M, st.Gh, r);
+        if (E > 0) load_rows<SE, N>(P.A + qp * P.sA, E, st.Ah, r);
     }
     {
         static_assert(C::oLq == 0, "the Lq stream runs on the LDS array's own chunk grid");
         const double *Lp = lds + C::oLq;
         constexpr int lastLq = tri(N - 1) + N - 2;          // Lq[N-1][N-2]: the last entry phase B reads
         LdsStream lq;
-        if (C::PF_ROWS && N > 1) stream_open(Lp, lq, tri(1), lastLq);
+        if (C::PF && N > 1) stream_open(Lp, lq, tri(1), lastLq);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
 #pragma unroll
             for (int k = 0; k < j; ++k) {
                 double ljk;
-                if (C::PF_ROWS) {
+                if (C::PF) {
                     // the next chunk's reads go out ahead of this chunk's FMAs -- for the last entries of a
                     // column that is the first chunk of column j + 1, above this column's closing barrier
                     if (stream_advance(Lp, lq, tri(j) + k, lastLq)) {
@@ -676,13 +642,11 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
             }
             // keep each column's LDS reads next to their FMAs (otherwise the scheduler may drift
             // the Ah chain away from the Gh chain and spill the Lq values in between)
-            if (C::PIN) {
 #pragma unroll
-                for (int s = 0; s < SE; ++s) pin(st.Ah[s][j]);
-                if (!C::SPLIT) {
+            for (int s = 0; s < SE; ++s) pin(st.Ah[s][j]);
+            if (!C::SPLIT) {
 #pragma unroll
-                    for (int s = 0; s < SM; ++s) pin(st.Gh[s][j]);
-                }
+                for (int s = 0; s < SM; ++s) pin(st.Gh[s][j]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -700,9 +664,6 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
 #pragma unroll
         for (int k = E - 1; k >= 0; --k) {
             const int sk = k >> 4, lk = k & 15, ck = R + k;
-#ifdef DQP_STAMPS_C      /* experiment: one stamp per reflector */
-            if (k < 15) { STAMPC(P, k); }
-#endif
             double u[N];
             double nrm2 = 0.0;
 #pragma unroll
@@ -719,22 +680,13 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
             const double iu = frcp(uck);
             const double tauk = uck * uck * frcp(nrm2 - alpha * vk);
             double *tl = lds + C::oTl + C::toff(k);
-            if (C::PIN) {
-                // one exec-masked region with immediate LDS offsets (the select-an-address form below
-                // costs an address VGPR per element, and LLVM then keeps all of them for phase G)
+            // one exec-masked region with immediate LDS offsets (selecting between the address and a dummy
+            // costs an address VGPR per element, and LLVM then keeps all of them for phase G)
 #pragma unroll
-                for (int c = 0; c < ck; ++c) u[c] *= iu;
-                if (r == 0) {
+            for (int c = 0; c < ck; ++c) u[c] *= iu;
+            if (r == 0) {
 #pragma unroll
-                    for (int c = 0; c < ck; ++c) tl[c] = u[c];
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < ck; ++c) {
-                    u[c] *= iu;
-                    double *dst = (r == 0) ? tl + c : dummy;
-                    *dst = u[c];
-                }
+                for (int c = 0; c < ck; ++c) tl[c] = u[c];
             }
             if (r == lk) { st.tau[sk] = tauk; st.rdu1[sk] = frcp(alpha); }
             // rows of Ah above k
@@ -764,21 +716,17 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
                     st.Gh[s][ck] -= tw;
                 }
             }
-            if (C::PIN) {           // next reflector's LDS traffic stays behind this one's arithmetic
+            // next reflector's LDS traffic stays behind this one's arithmetic
 #pragma unroll
-                for (int s = 0; s < SE; ++s) pin(st.Ah[s][ck]);
-                if (!C::SPLIT) {
+            for (int s = 0; s < SE; ++s) pin(st.Ah[s][ck]);
+            if (!C::SPLIT) {
 #pragma unroll
-                    for (int s = 0; s < SM; ++s) pin(st.Gh[s][ck]);
-                }
+                for (int s = 0; s < SM; ++s) pin(st.Gh[s][ck]);
             }
         }
-#ifdef DQP_STAMPS_C
-        STAMPC(P, 15);
-#endif
         __syncthreads();          // tails are read back as distributed vectors
         __builtin_amdgcn_sched_barrier(0);
-        if (C::EARLY) {
+        {   // the tails are final: the next piece of the context
             double *ws = P.workspace + qp * (long long)C::wsQP;
             lds_to_ctx<C::tailsz>(lds + C::oTl, ws + C::wTl, r);
         }
@@ -809,7 +757,6 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     if (C::SPLIT) {
         // B, C for G on its own: Gh = G Lq^-T, then the reflectors (tails in LDS, read row-uniformly)
         if (mpc) mpc_rows_G<SM, N>(P, M, st.Gh, r);
-        else if (C::STAGED) load_rows_staged<SM, N, (M * N) % 2 == 0>(P.G + qp * P.sG, M, st.Gh, r, lds + C::oTl);
         else load_rows<SM, N>(P.G + qp * P.sG, M, st.Gh, r);
         const double *Lp = relabel(lds + C::oLq);
 #pragma unroll
@@ -897,7 +844,7 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     DQP_PHASE_FENCE();
     STAMP(P, 4);
 
-    if (C::EARLY && !C::PARK) park_GU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
+    if (!C::PARK) park_GU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
     if (E > 0) {
         double *ws = P.workspace + qp * (long long)C::wsQP;
 #pragma unroll
@@ -906,10 +853,10 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
             if (k < E) { ws[C::wXy + k] = st.xy[s]; ws[C::wPy + k] = st.py[s]; ws[C::wW1 + k] = st.w1[s]; }
         }
     }
-    if (C::PARKWU && E > 0) {
-        // three register slots per N-space matrix: W and U leave the register file here (phase G
-        // needs the room for Lq Qf) and come back for the epilogue
-        if (C::PARK || !C::EARLY) park_GU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
+    if (E > 0) {
+        // W and U leave the register file here and come back for the epilogue: they are dead during the
+        // iteration, and at three register slots per N-space matrix phase G needs the room for Lq Qf
+        if (C::PARK) park_GU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
 #pragma unroll
         for (int s = 0; s < SM; ++s)
 #pragma unroll
@@ -957,10 +904,8 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
 #pragma unroll
                     for (int s = 0; s < SN; ++s) Ld[s][c] = fma(-w[s], uc, Ld[s][c]);
                 }
-                if (C::PIN) {
 #pragma unroll
-                    for (int s = 0; s < SN; ++s) { pin(Ld[s][0]); pin(Ld[s][ck]); }
-                }
+                for (int s = 0; s < SN; ++s) { pin(Ld[s][0]); pin(Ld[s][ck]); }
             }
         }
 #pragma unroll
@@ -984,19 +929,8 @@ __device__ __forceinline__ void setup(const KParams &P, long long qp, int r, dou
     DQP_PHASE_FENCE();
     STAMP(P, 5);
 
-    // H: the reflector tails are done for now: park them in the caller's workspace (read back
-    // for the epilogue), then Rm = Gz Gz^T goes, packed, into the same LDS region.
-    {
-        if (!C::EARLY) {
-            double *ws = P.workspace + qp * (long long)C::wsQP;
-            lds_to_ctx<C::tailsz>(lds + C::oTl, ws + C::wTl, r);
-            lds_to_ctx<tri(N)>(lds + C::oLq, ws + C::wLq, r);
-            if (!C::PARKWU) park_GU<C>(ws, st, r);
-#pragma unroll
-            for (int s = 0; s < SN; ++s)
-                if (r + 16 * s < N) ws[C::wRdq + r + 16 * s] = st.rdq[s];
-        }
-    }
+    // H: the reflector tails are done for now (they wait in the caller's workspace since phase C and are
+    // read back for the epilogue): Rm = Gz Gz^T goes, packed, into their LDS region.
     __syncthreads();
     {
         double *Rp = lds + C::oR;
@@ -1073,7 +1007,7 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
     if (E > 0 && reload_tails) ctx_fetch<C::tailsz>(P.workspace + qp * (long long)C::wsQP + C::wTl, tl, r);
     // recover x = Lq^-T Qf [w* ; xy],  y = U^-T (c* delta w1 - xy - py - W^T z*)
     double bw[SR], bs[SM], bz[SM];
-    if (C::PF_HEADS) {     // the parked iterate is each lane's own (vec_put): read under the tails' round trip
+    if (C::PF) {   // the parked iterate is each lane's own (vec_put): read under the tails' round trip
         vec_get<SR>(lds + C::oBw, bw, R, r);
         vec_get<SM>(lds + C::oBs, bs, M, r);
         vec_get<SM>(lds + C::oBz, bz, M, r);
@@ -1081,7 +1015,7 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
     __syncthreads();
     if (E > 0 && reload_tails) ctx_stash<C::tailsz>(lds + C::oTl, tl, r);
     __syncthreads();
-    if (!C::PF_HEADS) {
+    if (!C::PF) {
         vec_get<SR>(lds + C::oBw, bw, R, r);
         vec_get<SM>(lds + C::oBs, bs, M, r);
         vec_get<SM>(lds + C::oBz, bz, M, r);
@@ -1094,7 +1028,7 @@ __device__ __forceinline__ void epilogue(const KParams &P, long long qp, int r, 
     for (int s = 0; s < SE; ++s) yv[s] = 0.0;
     if (E > 0) {
         // (the finish pass has W and U from load_ctx)
-        if (C::PARKWU && reload_tails) unpark_WU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
+        if (reload_tails) unpark_WU<C>(P.workspace + qp * (long long)C::wsQP, st, r);
         shift_up<C>(st.xy, xh, r);
         apply_Qf<C>(lds, st.tau, xh, r);
         double wz[SE];
@@ -1544,7 +1478,7 @@ __global__ __launch_bounds__(64) void backward_kernel(KParams P)
             for (int s = 0; s < SM; ++s) T[s][j] = acc[s];
             __builtin_amdgcn_sched_barrier(0);
         }
-        lu_factor_solve<SM, M, DQP_LU_FOLD_RHS != 0>(T, rdu, dlam, r);
+        lu_factor_solve<SM, M>(T, rdu, dlam, r);
     }
     __builtin_amdgcn_sched_barrier(0);
     double dxh[SN], dnu[SE];

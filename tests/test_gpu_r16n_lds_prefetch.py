@@ -1,7 +1,7 @@
 """The LDS operand prefetch of the DPP-row kernels (csrc/dqp_r16_prims.h: the column ring of tri_solve / tri_solve_T /
 tri_mv; csrc/dqp_r16n.hip: the next reflector's tail in apply_Qf / apply_QfT, the 8-double stream of Lq entries in
 the setup's row solves, the epilogue's parked iterate read ahead of the tails' barriers).  The prefetched forms run the
-same floating-point operations on the same values as the plain ones (-DDQP_LDS_PREFETCH=0), so these tests pin,
+same floating-point operations on the same values as the plain ones (which the three-slot sizes keep), so these tests pin,
 straight through the C ABI,
   * forward and context backward against the CPU oracle at every compiled null-space size -- the two-slot sizes, the
     two three-slot sizes whose setup does the G pass on its own, and (10, 5, 3), whose ring of four columns is longer
