@@ -442,7 +442,7 @@ struct AsmP {
 __device__ __forceinline__ double jac_entry(const AsmP &P, const double *Jx, const double *Ju,
                                             const double *resc, int row, int col, bool clamp)
 {
-    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n;
+    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = AlRows{n, m, T, false}.neq();
     const int tc = col / nt, jc = col - tc * nt;
     if (row < neq) {
         const int t = row / n, r = row - t * n;
@@ -459,7 +459,9 @@ __device__ __forceinline__ double jac_entry(const AsmP &P, const double *Jx, con
 
 __global__ __launch_bounds__(256) void al_assemble_kernel(AsmP P)
 {
-    const int n = P.n, m = P.m, T = P.T, nt = n + m, nz = T * nt, neq = T * n, ncon = neq + 2 * T * m;
+    const int n = P.n, m = P.m, T = P.T, nt = n + m, nz = T * nt;
+    const AlRows R = {n, m, T, false};
+    const int ncon = R.ncon();
     const long long b = blockIdx.x;
     const double *Jx = P.Jx + b * (long long)(T - 1) * n * n, *Ju = P.Ju + b * (long long)(T - 1) * n * m;
     const double *resc = P.resc + b * (long long)ncon;
@@ -480,13 +482,13 @@ __global__ __launch_bounds__(256) void al_assemble_kernel(AsmP P)
             auto mu = [&](int row) { return lam[row] + rho * resc[row]; };
             double acc = 0.0;
             if (t < T - 1)
-                for (int r = 0; r < n; ++r) acc += jac_entry(P, Jx, Ju, resc, t * n + r, col, false) * mu(t * n + r);
+                for (int r = 0; r < n; ++r) acc += jac_entry(P, Jx, Ju, resc, R.eq(t) + r, col, false) * mu(R.eq(t) + r);
             if (j < n) {
-                if (t >= 1) acc += mu((t - 1) * n + j);
-                if (t == 0) acc += mu((T - 1) * n + j);
+                if (t >= 1) acc += mu(R.eq(t - 1) + j);
+                if (t == 0) acc += mu(R.eq(T - 1) + j);
             } else {
                 const int i = j - n;
-                acc += mu(neq + t * 2 * m + i) - mu(neq + t * 2 * m + m + i);
+                acc += mu(R.ctrl(t) + i) - mu(R.ctrl(t) + m + i);
             }
             if (P.Qd) acc += P.Qd[b * (long long)nz + col] * P.xu[b * (long long)nz + col] + P.q[b * (long long)nz + col];
             P.gterm[b * (long long)nz + col] = acc;
@@ -502,19 +504,17 @@ struct MeritP {
     const double *xu, *xn, *x0, *Qd, *q, *lam, *rho, *ul, *uu;
     double *merit;
     int B, n, m, T, ncand;
+    long long bsb, bst;         // bound layout (dqp_al_bounds.h), read with SB only
+    const double *xlo, *xhi;    // state box (dqp_al_merit_xbounds), read with XB only: lower / upper of (b, t, j) at
+    long long xsb, xst;         // [b xsb + t xst + j]; lam then carries the state rows, knot 0's included
 };
-// the argument of the strided kernel: + the bound layout (dqp_al_bounds.h).  The vector kernels keep their argument
-// struct, so that not even the offsets of their hidden kernel arguments move.
-struct MeritPS : MeritP { long long bsb, bst; };
-template <bool SB> using MeritArg = std::conditional_t<SB, MeritPS, MeritP>;
-// the argument of the kernel with state rows (dqp_al_merit_xbounds): + the state box, lower / upper of (b, t, j) at
-// [b xsb + t xst + j].  It grows at its end, so the two kernels above keep theirs.
-struct MeritPX : MeritPS { const double *xlo, *xhi; long long xsb, xst; };
 
-// SB: per-sample / per-knot bounds at [b bsb + t bst + i]; !SB: the n_ctrl-vector
-template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritArg<SB> P)
+// SB: per-sample / per-knot bounds at [b bsb + t bst + i], !SB: the n_ctrl-vector; XB: + the state rows
+template <bool SB, bool XB> __device__ __forceinline__ void merit_sweep(const MeritP &P)
 {
-    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, ncon = neq + 2 * T * m;
+    static_assert(SB || !XB, "with a state box both boxes are read through their strides");
+    const int n = P.n, m = P.m, T = P.T, nt = n + m;
+    const AlRows R = {n, m, T, XB};
     const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // (cand, problem)
     const int r = threadIdx.x & 15;
     const long long total = (long long)P.ncand * P.B;
@@ -522,78 +522,37 @@ template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritA
     const long long b = it % P.B;
     const double *xu = P.xu + it * (long long)T * nt, *xn = P.xn + it * (long long)(T - 1) * n;
     const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
-    const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
+    const double *lam = P.lam + b * (long long)R.ncon(), *x0 = P.x0 + b * (long long)n;
     const double rho = P.rho[b];
+    // with a state box the sample's rows of both boxes are taken once, in front of the sweep (the form that kernel was timed in)
+    const double *ul = P.ul + (XB ? b * P.bsb : 0), *uu = P.uu + (XB ? b * P.bsb : 0);
+    [[maybe_unused]] const double *xlo = XB ? P.xlo + b * P.xsb : nullptr, *xhi = XB ? P.xhi + b * P.xsb : nullptr;
     double acc = 0.0;
     for (int t = r; t < T; t += 16) {
         const double *z = xu + t * nt;
-        for (int j = 0; j < nt; ++j) acc += (0.5 * Qd[t * nt + j] * z[j] + q[t * nt + j]) * z[j];
+        for (int j = 0; j < nt; ++j) acc += al_cost_term(Qd[t * nt + j], q[t * nt + j], z[j]);
         for (int j = 0; j < n; ++j) {                       // equality row block of knot t
-            double res;
-            int row;
-            if (t < T - 1) { res = xu[(t + 1) * nt + j] - xn[t * n + j]; row = t * n + j; }
-            else { res = xu[j] - x0[j]; row = (T - 1) * n + j; }
-            acc += (0.5 * rho * res + lam[row]) * res;
-        }
-        for (int i = 0; i < m; ++i) {                       // box rows of knot t
-            double uut, ult;
-            if constexpr (SB) { uut = P.uu[b * P.bsb + t * P.bst + i]; ult = P.ul[b * P.bsb + t * P.bst + i]; }
-            else { uut = P.uu[i]; ult = P.ul[i]; }
-            const double u = z[n + i], up = u - uut, lo = ult - u;
-            const int row = neq + t * 2 * m + i;
-            acc += lam[row] * up + lam[row + m] * lo + 0.5 * rho * (fmax(up, 0.0) * fmax(up, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
-        }
-    }
-    acc = dqp::r16::row_sum(acc);
-    if (r == 0 && item < total) P.merit[item] = acc;
-}
-
-// The third instantiation: the same sweep with the state rows of dqp_al_bounds.h behind the control rows -- per knot
-// [x - x_upper (n), x_lower - x (n)], knot 0's included -- and both boxes read through their strides.  An overload on a
-// second template parameter with a body of its own: the two kernels above keep their names in a trace and their
-// instruction streams (sharing the body through a helper moved three of their instructions).
-template <bool SB, bool XB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritPX P)
-{
-    static_assert(SB && XB, "with a state box both boxes are read through their strides");
-    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, nxrow = neq + 2 * T * m, ncon = nxrow + 2 * T * n;
-    const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // (cand, problem)
-    const int r = threadIdx.x & 15;
-    const long long total = (long long)P.ncand * P.B;
-    const long long it = item < total ? item : total - 1;
-    const long long b = it % P.B;
-    const double *xu = P.xu + it * (long long)T * nt, *xn = P.xn + it * (long long)(T - 1) * n;
-    const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
-    const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
-    const double *ul = P.ul + b * P.bsb, *uu = P.uu + b * P.bsb, *xlo = P.xlo + b * P.xsb, *xhi = P.xhi + b * P.xsb;
-    const double rho = P.rho[b];
-    auto row_pair = [&](double v, double upper, double lower, double lam_up, double lam_lo) {
-        const double up = v - upper, lo = lower - v;
-        return lam_up * up + lam_lo * lo + 0.5 * rho * (fmax(up, 0.0) * fmax(up, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
-    };
-    double acc = 0.0;
-    for (int t = r; t < T; t += 16) {
-        const double *z = xu + t * nt;
-        for (int j = 0; j < nt; ++j) acc += (0.5 * Qd[t * nt + j] * z[j] + q[t * nt + j]) * z[j];
-        for (int j = 0; j < n; ++j) {                       // equality row block of knot t
-            double res;
-            int row;
-            if (t < T - 1) { res = xu[(t + 1) * nt + j] - xn[t * n + j]; row = t * n + j; }
-            else { res = xu[j] - x0[j]; row = (T - 1) * n + j; }
-            acc += (0.5 * rho * res + lam[row]) * res;
+            const double res = t < T - 1 ? xu[(t + 1) * nt + j] - xn[t * n + j] : xu[j] - x0[j];
+            acc += al_eq_term(rho, lam[R.eq(t) + j], res);
         }
         for (int i = 0; i < m; ++i) {                       // control rows of knot t
-            const int row = neq + t * 2 * m + i;
-            acc += row_pair(z[n + i], uu[t * P.bst + i], ul[t * P.bst + i], lam[row], lam[row + m]);
+            const int row = R.ctrl(t) + i;
+            const long long o = XB ? t * P.bst + i : al_bound_at<SB>(b, t, i, P.bsb, P.bst);
+            acc += al_pair_term(rho, lam[row], lam[row + m], z[n + i] - uu[o], ul[o] - z[n + i]);
         }
-        for (int j = 0; j < n; ++j) {                       // state rows of knot t
-            const int row = nxrow + t * 2 * n + j;
-            acc += row_pair(z[j], xhi[t * P.xst + j], xlo[t * P.xst + j], lam[row], lam[row + n]);
+        if constexpr (XB) {
+            for (int j = 0; j < n; ++j) {                   // state rows of knot t
+                const int row = R.state(t) + j;
+                acc += al_pair_term(rho, lam[row], lam[row + n], z[j] - xhi[t * P.xst + j], xlo[t * P.xst + j] - z[j]);
+            }
         }
     }
     acc = dqp::r16::row_sum(acc);
     if (r == 0 && item < total) P.merit[item] = acc;
 }
-
+// the entry points, under the names a trace shows: <SB> without a state box, <true, true> with one
+template <bool SB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritP P) { merit_sweep<SB, false>(P); }
+template <bool SB, bool XB> __global__ __launch_bounds__(256) void al_merit_kernel(MeritP P) { merit_sweep<SB, XB>(P); }
 
 // ------------------------------------------------------------------------------------------
 // NewtonAL with a registered device model: the Python glue of al_utils.NewtonAL.forward
@@ -619,66 +578,49 @@ __device__ __forceinline__ void lin_knot(const double *z, double dt, double *xn,
         for (int c = 0; c < NU; ++c) Ju[r * NU + c] = o[r].d[NX + c];
     }
 }
-template <class Map>
-__device__ __forceinline__ void step_knot(const double *xs, const double *us, double dt, double *xn)
-{
-    double xa[Map::NX], ua[Map::NU], o[Map::NX];
-#pragma unroll
-    for (int k = 0; k < Map::NX; ++k) xa[k] = xs[k];
-#pragma unroll
-    for (int k = 0; k < Map::NU; ++k) ua[k] = us[k];
-    Map::template step<double>(xa, ua, dt, o);
-#pragma unroll
-    for (int k = 0; k < Map::NX; ++k) xn[k] = o[k];
-}
 
 struct LinP {
     const double *xu, *x0, *ul, *uu;
     double *Jx, *Ju, *resc;
     double dt;
     int B, n, m, T, dyn;
+    long long bsb, bst;         // bound layout (dqp_al_bounds.h), read with SB only
 };
-struct LinPS : LinP { long long bsb, bst; };        // + the bound layout, for the strided kernel
-template <bool SB> using LinArg = std::conditional_t<SB, LinPS, LinP>;
+constexpr int LIN_NX = 8, LIN_NU = 2;       // the largest knot of the dense form (newton_dense refuses beyond)
 
 // one thread per (problem, knot): dynamics + Jacobians of the knot, its equality rows
 // x_{t+1} - f(x_t, u_t) (or x_0 - x0 for the last block) and its clamped box rows
-template <bool SB> __global__ __launch_bounds__(256) void al_linearize_kernel(LinArg<SB> P)
+template <bool SB> __global__ __launch_bounds__(256) void al_linearize_kernel(LinP P)
 {
-    const int n = P.n, m = P.m, T = P.T, nt = n + m, neq = T * n, ncon = neq + 2 * T * m;
+    const int n = P.n, m = P.m, T = P.T, nt = n + m;
+    const AlRows R = {n, m, T, false};
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)P.B * T) return;
     const long long b = idx / T;
     const int t = (int)(idx - b * T);
     const double *z = P.xu + (b * T + t) * nt;
-    double *resc = P.resc + b * ncon;
+    double *resc = P.resc + b * R.ncon();
     if (t < T - 1) {
-        double xn[8], Jx[64], Ju[16];
-        switch (P.dyn) {
-        case DQP_DYN_PENDULUM1L: lin_knot<dqp::dyn::Robot<dqp::dyn::Pendulum1l>>(z, P.dt, xn, Jx, Ju); break;
-        case DQP_DYN_CARTPOLE1L: lin_knot<dqp::dyn::Robot<dqp::dyn::Cartpole1l>>(z, P.dt, xn, Jx, Ju); break;
-        case DQP_DYN_CARTPOLE2L: lin_knot<dqp::dyn::Robot<dqp::dyn::Cartpole2l>>(z, P.dt, xn, Jx, Ju); break;
-        case DQP_DYN_PENDULUM_EULER: lin_knot<dqp::dyn::PendulumEuler>(z, P.dt, xn, Jx, Ju); break;
-        case DQP_DYN_INTEGRATOR: lin_knot<dqp::dyn::Integrator>(z, P.dt, xn, Jx, Ju); break;
-        default: lin_knot<dqp::dyn::PendulumDx>(z, P.dt, xn, Jx, Ju); break;
-        }
         double *oJx = P.Jx + (b * (T - 1) + t) * n * n, *oJu = P.Ju + (b * (T - 1) + t) * n * m;
-        for (int i = 0; i < n * n; ++i) oJx[i] = Jx[i];
-        for (int i = 0; i < n * m; ++i) oJu[i] = Ju[i];
-        for (int i = 0; i < n; ++i) resc[t * n + i] = z[nt + i] - xn[i];
+        dqp::dyn::visit<int>(P.dyn, 0, [&](auto model) {        // the host has checked the id and that (n, m) are its sizes
+            using Map = typename decltype(model)::Map;
+            if constexpr (Map::NX <= LIN_NX && Map::NU <= LIN_NU) {
+                double xn[Map::NX];
+                lin_knot<Map>(z, P.dt, xn, oJx, oJu);
+#pragma unroll
+                for (int i = 0; i < Map::NX; ++i) resc[R.eq(t) + i] = z[nt + i] - xn[i];
+            }
+            return 0;
+        });
     } else {
         const double *z0 = P.xu + b * T * nt;
-        for (int i = 0; i < n; ++i) resc[(T - 1) * n + i] = z0[i] - P.x0[b * n + i];
+        for (int i = 0; i < n; ++i) resc[R.eq(t) + i] = z0[i] - P.x0[b * n + i];
     }
     for (int i = 0; i < m; ++i) {
         const double u = z[n + i];
-        if constexpr (SB) {
-            resc[neq + t * 2 * m + i] = fmax(u - P.uu[b * P.bsb + t * P.bst + i], 0.0);
-            resc[neq + t * 2 * m + m + i] = fmax(P.ul[b * P.bsb + t * P.bst + i] - u, 0.0);
-        } else {
-            resc[neq + t * 2 * m + i] = fmax(u - P.uu[i], 0.0);
-            resc[neq + t * 2 * m + m + i] = fmax(P.ul[i] - u, 0.0);
-        }
+        const long long o = al_bound_at<SB>(b, t, i, P.bsb, P.bst);
+        resc[R.ctrl(t) + i] = fmax(u - P.uu[o], 0.0);
+        resc[R.ctrl(t) + m + i] = fmax(P.ul[o] - u, 0.0);
     }
 }
 
@@ -692,20 +634,15 @@ struct LsAP {
     double *xu_w, *merit_cur, *status;
     int32_t *fail;
     const int32_t *info;
+    long long bsb, bst;         // bound layout (dqp_al_bounds.h), read by the StridedBounds<> instantiations only
+    const double *xlo, *xhi;    // state box, read by the BoxBounds<> instantiations only (else NULL); lam then carries
+    long long xsb, xst;         // 2 T n more rows
 };
-// + the bound layout (dqp_al_bounds.h): the argument of the StridedBounds<> instantiations, and what the host code
-// carries; a vector instantiation is launched with the LsAP part of it
-struct LsAPS : LsAP { long long bsb, bst; };
-// + the state box (dqp_al_bounds.h: BoxBounds<>): the argument of the BoxBounds<> instantiations, and what the host code
-// carries (xlo == NULL: no state box); the other instantiations keep their argument types and sizes
-struct LsAPX : LsAPS { const double *xlo, *xhi; long long xsb, xst; };
-template <class Map> using LsArg =
-    std::conditional_t<box_bounds<Map>::value, LsAPX, std::conditional_t<strided_bounds<Map>::value, LsAPS, LsAP>>;
 // the merit of `ncand` candidates xu + 2^-k upd into `merit` (ncand = 0: of xu itself).  The folded selection (xu_w,
 // merit_cur, status, fail, info) is the caller's to set.
-LsAPX ls_args(const AlProblem &v, const double *xu, const double *upd, double *merit, int ncand)
+LsAP ls_args(const AlProblem &v, const double *xu, const double *upd, double *merit, int ncand)
 {
-    LsAPX P = dqp::boxed_args<LsAPX>(v);
+    LsAP P = dqp::boxed_args<LsAP>(v);
     P.xu = xu; P.upd = upd; P.merit = merit; P.dt = v.dt; P.n = v.n; P.m = v.m; P.ncand = ncand; P.dyn = v.model;
     return P;
 }
@@ -718,12 +655,12 @@ LsAPX ls_args(const AlProblem &v, const double *xu, const double *upd, double *m
 //   phase B  one knot per lane: the model step from the knot in LDS (odd stride: conflict-free),
 //            residual against the next knot in LDS, multiplier and penalty terms
 template <class Map>
-__global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
+__global__ __launch_bounds__(256) void al_ls_kernel(LsAP P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     __shared__ double ls_lds[16 * 17 * ZS];
     constexpr bool XB = box_bounds<Map>::value;
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0);
+    const int T = P.T, neq = AlRows{n, m, T, XB}.neq(), ncon = AlRows{n, m, T, XB}.ncon();
     const int nc = P.ncand > 0 ? P.ncand : 1;
     const int slot = threadIdx.x >> 4, r = threadIdx.x & 15;
     const long long item = (long long)blockIdx.x * 16 + slot;
@@ -731,8 +668,9 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
     const long long it = item < total ? item : total - 1;
     const long long b = it % P.B;
     const int k = (int)(it / P.B);
-    const double step = P.ncand > 0 ? (double)exp2f(-(float)k) : 0.0;      // float steps, as the reference
-    const double *xu = P.xu + b * (long long)T * nt, *up = P.upd + b * (long long)T * nt;
+    const double step = P.ncand > 0 ? al_step(k) : 0.0;
+    // ncand = 0: no update exists yet and what lies in its place may be NaN (0 NaN is not 0): step 0 along the iterate itself
+    const double *xu = P.xu + b * (long long)T * nt, *up = P.ncand > 0 ? P.upd + b * (long long)T * nt : xu;
     const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
     const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
     const double rho = P.rho[b];
@@ -748,20 +686,18 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
             if (t == 0 && j < n) z = x0[j];
             zb[tl * ZS + j] = z;
             if (tl < 16) {
-                acc += (0.5 * Qd[ge] * z + q[ge]) * z;
+                acc += al_cost_term(Qd[ge], q[ge], z);
                 if (j >= n) {
                     const int i = j - n, row = neq + t * 2 * m + i;
                     double uut, ult;
                     if constexpr (SB) { uut = P.uu[b * P.bsb + t * P.bst + i]; ult = P.ul[b * P.bsb + t * P.bst + i]; }
                     else { uut = P.uu[i]; ult = P.ul[i]; }
                     const double hi = z - uut, lo = ult - z;
-                    acc += lam[row] * hi + lam[row + m] * lo +
-                           0.5 * rho * (fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
+                    acc += al_pair_term(rho, lam[row], lam[row + m], hi, lo);
                 } else if constexpr (XB) {      // the state rows of the element, into the same accumulator
                     const int row = neq + 2 * T * m + t * 2 * n + j;
                     const double hi = z - P.xhi[b * P.xsb + t * P.xst + j], lo = P.xlo[b * P.xsb + t * P.xst + j] - z;
-                    acc += lam[row] * hi + lam[row + n] * lo +
-                           0.5 * rho * (fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0));
+                    acc += al_pair_term(rho, lam[row], lam[row + n], hi, lo);
                 }
             }
         }
@@ -775,7 +711,7 @@ __global__ __launch_bounds__(256) void al_ls_kernel(LsArg<Map> P)
 #pragma unroll
             for (int j = 0; j < n; ++j) {
                 const double res = zb[(r + 1) * ZS + j] - xn[j];
-                acc += (0.5 * rho * res + lam[t * n + j]) * res;
+                acc += al_eq_term(rho, lam[t * n + j], res);
             }
         }
         __syncthreads();
@@ -822,13 +758,17 @@ __device__ __forceinline__ void group_sync()
 }
 
 template <class Map, int TPI, int TMAX>
-__global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12) ? 2 : 1) void al_ls_group_kernel(LsArg<Map> P)
+__global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12) ? 2 : 1) void al_ls_group_kernel(LsAP P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m, ZS = nt | 1;
     constexpr int EPL = (TMAX * nt + TPI - 1) / TPI;       // elements of the (T, nt) arrays per lane, T <= TMAX
     extern __shared__ double lsg_lds[];
     constexpr bool XB = box_bounds<Map>::value;
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0), nzq = T * nt;
+    const int T = P.T, nzq = T * nt;
+    const AlRows R = {n, m, T, XB};
+    // This kernel alone spells its rows out from neq (AlRows of dqp_al_bounds.h has the layout): the quadrotor with a state
+    // box sits at 256 registers, and R.ctrl / R.state inside its loops raised its spills
+    const int neq = R.neq();
     const int nc = P.ncand > 0 ? P.ncand : 1;
     const int grp = threadIdx.x / TPI, r = threadIdx.x % TPI;
     const long long pb = (long long)blockIdx.x * (256 / TPI) + grp;
@@ -836,7 +776,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     const long long b = live ? pb : P.B - 1;
     const double *xu = P.xu + b * (long long)nzq, *up = P.upd + b * (long long)nzq;
     const double *Qd = P.Qd + b * (long long)nzq, *q = P.q + b * (long long)nzq;
-    const double *lam = P.lam + b * (long long)ncon, *x0 = P.x0 + b * (long long)n;
+    const double *lam = P.lam + b * (long long)R.ncon(), *x0 = P.x0 + b * (long long)n;
     const double rho = P.rho[b];
     double *zb = lsg_lds + (size_t)grp * T * ZS;
     // ---- the problem, once: element e = r + TPI i of the (T, nt) arrays; the box rows (multipliers, bounds) only exist
@@ -886,12 +826,9 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
         const int ec = t * nt + n + iu, row = neq + t * 2 * m + iu;
         cx[i] = ok ? xu[ec] : 0.0; cu[i] = (ok && P.ncand > 0) ? up[ec] : 0.0;
         lu[i] = ok ? lam[row] : 0.0; ll[i] = ok ? lam[row + m] : 0.0;
-        if constexpr (strided_bounds<Map>::value) {       // the element's own knot: once, with its multipliers
-            const long long bo = b * P.bsb + t * P.bst + iu;
-            hi[i] = ok ? P.uu[bo] : INFINITY; lo[i] = ok ? P.ul[bo] : -INFINITY;
-        } else {
-            hi[i] = ok ? P.uu[iu] : INFINITY; lo[i] = ok ? P.ul[iu] : -INFINITY;
-        }
+        // strided: the element's own knot, once, with its multipliers
+        const long long bo = al_bound_at<strided_bounds<Map>::value>(b, t, iu, P.bsb, P.bst);
+        hi[i] = ok ? P.uu[bo] : INFINITY; lo[i] = ok ? P.ul[bo] : -INFINITY;
     }
     // multipliers of the lane's dynamics rows: registers, or -- long knots -- the group's LDS rows behind its iterate
     double ly[POLY ? 1 : n];
@@ -907,7 +844,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     int arg = 0;
     bool isnan_ = false;
     for (int k = blockIdx.y; k < nc; k += gridDim.y) {
-        const double step = P.ncand > 0 ? (double)exp2f(-(float)k) : 0.0;    // float steps, as the reference
+        const double step = P.ncand > 0 ? al_step(k) : 0.0;
         double acc = POLY ? fma(step, fma(step, c2, c1), c0) : 0.0;
 #pragma unroll
         for (int i = 0; i < EPL; ++i) {
@@ -916,7 +853,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
                 const int t = e / nt, j = e - t * nt;
                 const double z = fma(step, eu[i], ex[i]);
                 zb[t * ZS + j] = z;
-                if constexpr (!POLY) acc += (0.5 * eq[i] * z + el[i]) * z;
+                if constexpr (!POLY) acc += al_cost_term(eq[i], el[i], z);
                 if constexpr (XB) {         // the element's state rows, into the accumulator the lane already owns
                     if (j < n) {
                         double h, l, mu, ml;
@@ -925,8 +862,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
                             const int row = neq + 2 * T * m + t * 2 * n + j;
                             h = xhb[t * P.xst + j]; l = xlb[t * P.xst + j]; mu = lam[row]; ml = lam[row + n];
                         }
-                        const double vh = z - h, vl = l - z;
-                        acc += mu * vh + ml * vl + 0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
+                        acc += al_pair_term(rho, mu, ml, z - h, l - z);
                     }
                 }
             }
@@ -935,8 +871,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
         for (int i = 0; i < UPL; ++i) {
             if (r + TPI * i < T * m) {
                 const double z = fma(step, cu[i], cx[i]);
-                const double vh = z - hi[i], vl = lo[i] - z;
-                acc += lu[i] * vh + ll[i] * vl + 0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
+                acc += al_pair_term(rho, lu[i], ll[i], z - hi[i], lo[i] - z);
             }
         }
         group_sync();
@@ -948,7 +883,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
 #pragma unroll
             for (int j = 0; j < n; ++j) {
                 const double res = zb[(r + 1) * ZS + j] - xn[j];
-                acc += (0.5 * rho * res + (POLY ? lyb[j] : ly[j])) * res;
+                acc += al_eq_term(rho, POLY ? lyb[j] : ly[j], res);
             }
         }
         group_sync();
@@ -971,7 +906,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
             if (P.info && P.info[b] != 0) atomicOr(P.fail, 1);  // Cholesky failed: the caller re-runs the slow path
         }
         if (take && live) {
-            const double sb = (double)exp2f(-(float)arg);
+            const double sb = al_step(arg);
             double *xw = P.xu_w + b * (long long)nzq;
 #pragma unroll
             for (int i = 0; i < EPL; ++i) {
@@ -982,7 +917,7 @@ __global__ __launch_bounds__(256, ((TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI 
     }
 }
 
-template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPX &P, hipStream_t st)
+template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAP &P, hipStream_t st)
 {
     constexpr int ZS = (Map::NX + Map::NU) | 1, G = 256 / TPI;
     constexpr bool POLY = (TMAX * (Map::NX + Map::NU) + TPI - 1) / TPI >= 12;
@@ -991,11 +926,11 @@ template <class Map, int TPI, int TMAX = TPI> int launch_ls_group(const LsAPX &P
     // at least ~2 wavefronts per SIMD where the batch alone does not give them: split the candidates
     unsigned split = 1;
     if (P.ncand > 1) while (split < 4 && (unsigned long long)blocks * 4 * split < 2048) split *= 2;
-    DQP_LAUNCH((al_ls_group_kernel<Map, TPI, TMAX>), dim3(blocks, split), dim3(256), lds, st, static_cast<const LsArg<Map> &>(P));
+    DQP_LAUNCH((al_ls_group_kernel<Map, TPI, TMAX>), dim3(blocks, split), dim3(256), lds, st, P);
     return (P.xu_w && split == 1 && P.ncand > 0) ? 2 : DQP_OK;     // 2: the selection happened in the kernel
 }
 
-template <class Map> int launch_ls_t(const LsAPX &P, hipStream_t st)
+template <class Map> int launch_ls_t(const LsAP &P, hipStream_t st)
 {
     // the model phase keeps T - 1 lanes of a group busy: four lanes for the shortest horizons (config 5: T = 5)
     if (P.T <= 5) return launch_ls_group<Map, 4, 5>(P, st);
@@ -1003,11 +938,11 @@ template <class Map> int launch_ls_t(const LsAPX &P, hipStream_t st)
     if (P.T <= 16) return launch_ls_group<Map, 16>(P, st);
     if (P.T <= 32) return launch_ls_group<Map, 32>(P, st);
     const long long items = (long long)(P.ncand > 0 ? P.ncand : 1) * P.B;
-    DQP_LAUNCH(al_ls_kernel<Map>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, static_cast<const LsArg<Map> &>(P));
+    DQP_LAUNCH(al_ls_kernel<Map>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, P);
     return DQP_OK;
 }
 
-int launch_ls(const LsAPX &P, hipStream_t st)
+int launch_ls(const LsAP &P, hipStream_t st)
 {
     return dqp::dyn::visit<int>(P.dyn, DQP_ERR_BAD_ARG, [&](auto model) {
         using Map = typename decltype(model)::Map;
@@ -1043,7 +978,7 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
 {
     constexpr int n = Map::NX, m = Map::NU, nt = n + m;
     constexpr bool XB = box_bounds<Map>::value;
-    const int T = P.T, neq = T * n, ncon = neq + 2 * T * m + (XB ? 2 * T * n : 0);
+    const int T = P.T, neq = AlRows{n, m, T, XB}.neq(), ncon = AlRows{n, m, T, XB}.ncon();
     const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int r = threadIdx.x & 15;
     const long long b = item < P.B ? item : P.B - 1;
@@ -1058,7 +993,7 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
         double z[nt], xn[n];
 #pragma unroll
         for (int j = 0; j < nt; ++j) z[j] = xu[t * nt + j];
-        for (int j = 0; j < nt; ++j) cost += (0.5 * Qd[t * nt + j] * z[j] + q[t * nt + j]) * z[j];
+        for (int j = 0; j < nt; ++j) cost += al_cost_term(Qd[t * nt + j], q[t * nt + j], z[j]);
         if (t < T - 1) {
             Map::template step<double>(z, z + n, P.dt, xn);
             for (int j = 0; j < n; ++j) {
@@ -1079,7 +1014,7 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
             else { uut = P.uu[i]; ult = P.ul[i]; }
             const double u = z[n + i], hi = u - uut, lo = ult - u;
             const int row = neq + t * 2 * m + i;
-            rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
+            rn2 += al_pair_sq(hi, lo);
             if (live) {
                 ln[row] = fmax(lam[row] + rho * hi, 0.0);               // AL_mpc.py:300-301
                 ln[row + m] = fmax(lam[row + m] + rho * lo, 0.0);
@@ -1089,7 +1024,7 @@ __global__ __launch_bounds__(256) void al_outer_kernel(OutP P)
             for (int j = 0; j < n; ++j) {
                 const double hi = z[j] - P.xhi[b * P.xsb + t * P.xst + j], lo = P.xlo[b * P.xsb + t * P.xst + j] - z[j];
                 const int row = neq + 2 * T * m + t * 2 * n + j;
-                rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
+                rn2 += al_pair_sq(hi, lo);
                 if (live) {
                     ln[row] = fmax(lam[row] + rho * hi, 0.0);
                     ln[row + n] = fmax(lam[row + n] + rho * lo, 0.0);
@@ -1117,9 +1052,11 @@ struct StartP {
     int32_t *fail;          // al_iter Cholesky-failure flags, cleared here
     int nfail;
 };
-__global__ __launch_bounds__(256) void al_start_kernel(StartP P)
+// XB: a state box -- the multipliers and the history rows are 2 T n wider, and the norms and the scaling of the warm start
+// run over all of them
+template <bool XB> __device__ __forceinline__ void start_body(const StartP &P)
 {
-    const int n = P.n, m = P.m, nt = n + m, T = P.T, ncon = T * n + 2 * T * m;
+    const int n = P.n, m = P.m, nt = n + m, T = P.T, ncon = AlRows{n, m, T, XB}.ncon();
     const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int r = threadIdx.x & 15;
     const long long b = item < P.B ? item : P.B - 1;
@@ -1137,60 +1074,15 @@ __global__ __launch_bounds__(256) void al_start_kernel(StartP P)
     }
     const double cost0 = 0.5 * dqp::r16::row_sum(quad) + dqp::r16::row_sum(lin);       // al_utils.compute_cost, diagonal cost
     const double *lam = P.lam_in + b * (long long)ncon;
-    double scale = 1.0, rho = P.rho_in[b];
-    if (P.K > 0) {
-        int pick = P.K - 1;                                   // torch.max of an all-False column: index 0 = the newest
-        for (int k = P.K - 1; k >= 0; --k)
-            if (P.hist_cost[(long long)k * P.B + b] < cost0) { pick = k; break; }
-        const double *lh = P.hist_lam + ((long long)pick * P.B + b) * ncon;
-        double nh = 0.0, nl = 0.0;
-        for (int e = r; e < ncon; e += 16) { nh += lh[e] * lh[e]; nl += lam[e] * lam[e]; }
-        scale = sqrt(dqp::r16::row_sum(nh)) / sqrt(dqp::r16::row_sum(nl));
-        rho = P.hist_rho[(long long)pick * P.B + b];
-    }
+    const AlWarm w = al_warm_start(P.K, P.B, b, ncon, cost0, P.hist_cost, P.hist_lam, P.hist_rho, lam, P.rho_in[b], r, 16,
+                                   [](double v) { return dqp::r16::row_sum(v); });
     if (!live) return;
     double *l0 = P.lam0 + b * (long long)ncon;
-    for (int e = r; e < ncon; e += 16) l0[e] = P.K > 0 ? lam[e] * scale : lam[e];
-    if (r == 0) { P.cost0[b] = cost0; P.rho0[b] = rho; }
+    for (int e = r; e < ncon; e += 16) l0[e] = P.K > 0 ? lam[e] * w.scale : lam[e];
+    if (r == 0) { P.cost0[b] = cost0; P.rho0[b] = w.rho; }
 }
-// The same with a state box: the multipliers and the history rows are 2 T n wider, and the norms and the scaling of the warm
-// start run over all of them.  A kernel of its own, so that al_start_kernel stays the code it was.
-__global__ __launch_bounds__(256) void al_start_xbounds_kernel(StartP P)
-{
-    const int n = P.n, m = P.m, nt = n + m, T = P.T, ncon = T * n + 2 * T * m + 2 * T * n;
-    const long long item = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int r = threadIdx.x & 15;
-    const long long b = item < P.B ? item : P.B - 1;
-    const bool live = item < P.B;
-    if (blockIdx.x == 0 && (int)threadIdx.x < P.nfail) P.fail[threadIdx.x] = 0;
-    double *xu = P.xu + b * (long long)T * nt;
-    const double *Qd = P.Qd + b * (long long)T * nt, *q = P.q + b * (long long)T * nt;
-    double quad = 0.0, lin = 0.0;
-    for (int e = r; e < T * nt; e += 16) {
-        const int t = e / nt, j = e - t * nt;
-        const double v = j < n ? P.x_init[(b * T + t) * n + j] : P.u_init[(b * T + t) * m + (j - n)];
-        if (live) xu[e] = v;
-        quad += v * Qd[e] * v;
-        lin += q[e] * v;
-    }
-    const double cost0 = 0.5 * dqp::r16::row_sum(quad) + dqp::r16::row_sum(lin);       // al_utils.compute_cost, diagonal cost
-    const double *lam = P.lam_in + b * (long long)ncon;
-    double scale = 1.0, rho = P.rho_in[b];
-    if (P.K > 0) {
-        int pick = P.K - 1;                                   // torch.max of an all-False column: index 0 = the newest
-        for (int k = P.K - 1; k >= 0; --k)
-            if (P.hist_cost[(long long)k * P.B + b] < cost0) { pick = k; break; }
-        const double *lh = P.hist_lam + ((long long)pick * P.B + b) * ncon;
-        double nh = 0.0, nl = 0.0;
-        for (int e = r; e < ncon; e += 16) { nh += lh[e] * lh[e]; nl += lam[e] * lam[e]; }
-        scale = sqrt(dqp::r16::row_sum(nh)) / sqrt(dqp::r16::row_sum(nl));
-        rho = P.hist_rho[(long long)pick * P.B + b];
-    }
-    if (!live) return;
-    double *l0 = P.lam0 + b * (long long)ncon;
-    for (int e = r; e < ncon; e += 16) l0[e] = P.K > 0 ? lam[e] * scale : lam[e];
-    if (r == 0) { P.cost0[b] = cost0; P.rho0[b] = rho; }
-}
+__global__ __launch_bounds__(256) void al_start_kernel(StartP P) { start_body<false>(P); }
+__global__ __launch_bounds__(256) void al_start_xbounds_kernel(StartP P) { start_body<true>(P); }
 
 int launch_outer(const OutP &P, hipStream_t st)
 {
@@ -1221,18 +1113,11 @@ __global__ __launch_bounds__(64) void al_select_kernel(SelP P)
     // loads and a wavefront reduction instead of one lane walking ncand dependent loads (11 us -> launch-bound)
     const int lane = threadIdx.x;
     const bool has = lane < P.ncand;
-    const double v = has ? P.merit[(long long)lane * P.B + b] : INFINITY;
-    const unsigned long long nanmask = __builtin_amdgcn_ballot_w64(has && v != v);
-    double m = (v != v) ? INFINITY : v;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
-    const unsigned long long eq = __builtin_amdgcn_ballot_w64(has && v == m);
-    const int arg = nanmask ? (int)__builtin_ctzll(nanmask) : (eq ? (int)__builtin_ctzll(eq) : 0);
-    const double best = __shfl(v, arg, 64);
-    const bool take = best < P.merit_cur[b];
-    const double s_step = (double)exp2f(-(float)arg);
+    const AlBest best = al_wave_argmin(has ? P.merit[(long long)lane * P.B + b] : INFINITY, has);
+    const bool take = best.merit < P.merit_cur[b];
+    const double s_step = al_step(best.arg);
     if (lane == 0) {
-        P.merit_cur[b] = best;                              // new_merit regardless of acceptance
+        P.merit_cur[b] = best.merit;                        // new_merit regardless of acceptance
         if (P.status) P.status[b] = take ? 1.0 : 0.0;
         if (P.info && P.info[b] != 0) atomicOr(P.fail, 1);  // Cholesky failed: the caller re-runs the slow path
     }
@@ -1268,24 +1153,23 @@ int launch_newton(const AlP &P, size_t lds, void *stream)
 // The workspace of dqp_al_newton_solve in its two forms (include/dqp.h, "Extents"), carved and sized from ONE member
 // list.  The last array, info, is nbatch int32 in a slot of nbatch doubles, so every array before it starts on a multiple
 // of 8 bytes and nothing lies behind it.
-constexpr int N_LINESEARCH = 20;                // line-search candidates 2^-k, k = 0 .. 19 (al_utils.py:503-527)
 struct NewtonWork {
     double *Jx, *Ju, *resc, *Jc, *grad;         // the dense form only
-    double *upd, *merit, *merit_cur;            // update, N_LINESEARCH candidate merits, current merit
+    double *upd, *merit, *merit_cur;            // update, AL_NCAND candidate merits, current merit
     int32_t *info;
     size_t doubles;                             // of the form, per problem
 };
 // The arrays of a batch of B at `base`, in the order they lie; (NULL, 0): the size alone
 NewtonWork newton_work(void *base, size_t B, bool banded, size_t n, size_t m, size_t T)
 {
-    const size_t nz = T * (n + m), ncon = T * n + 2 * T * m;
+    const size_t nz = T * (n + m), ncon = AlRows{(int)n, (int)m, (int)T, false}.ncon();   // the dense form has no state box
     NewtonWork w = {};
     auto take = [&](auto *&array, size_t per_problem) {
         array = reinterpret_cast<std::remove_reference_t<decltype(array)>>((double *)base + B * w.doubles);
         w.doubles += per_problem;
     };
     if (!banded) { take(w.Jx, (T - 1) * n * n); take(w.Ju, (T - 1) * n * m); take(w.resc, ncon); take(w.Jc, ncon * nz); take(w.grad, nz); }
-    take(w.upd, nz); take(w.merit, N_LINESEARCH); take(w.merit_cur, 1); take(w.info, 1);
+    take(w.upd, nz); take(w.merit, AL_NCAND); take(w.merit_cur, 1); take(w.info, 1);
     return w;
 }
 
@@ -1345,16 +1229,16 @@ dqp_al_assemble(const dqp_al_mpc_dims *d, const double *Jx, const double *Ju, co
     return launched();
 }
 
-// Both merit entries behind their front checks.  A kernel without state rows or strides gets the MeritPS / MeritP part of P.
+// Both merit entries behind their front checks
 static int merit_launch(const AlProblem &v, int32_t ncand, const double *xu, const double *x_next, double *merit)
 {
     if (ncand == 0) return DQP_OK;
     if (const int r = v.ready(xu && x_next && merit); r != 1) return r;
-    MeritPX P = dqp::boxed_args<MeritPX>(v);
+    MeritP P = dqp::boxed_args<MeritP>(v);
     P.xu = xu; P.xn = x_next; P.merit = merit; P.n = v.n; P.m = v.m; P.ncand = ncand;
     const dim3 grid((unsigned)(((long long)ncand * v.B + 15) / 16));
-    if (!v.has_x && v.strided()) DQP_LAUNCH(al_merit_kernel<true>, grid, dim3(256), 0, v.stream, static_cast<const MeritPS &>(P));
-    else if (!v.has_x) DQP_LAUNCH(al_merit_kernel<false>, grid, dim3(256), 0, v.stream, static_cast<const MeritP &>(P));
+    if (!v.has_x && v.strided()) DQP_LAUNCH(al_merit_kernel<true>, grid, dim3(256), 0, v.stream, P);
+    else if (!v.has_x) DQP_LAUNCH(al_merit_kernel<false>, grid, dim3(256), 0, v.stream, P);
     else DQP_LAUNCH((al_merit_kernel<true, true>), grid, dim3(256), 0, v.stream, P);
     return launched();
 }
@@ -1398,11 +1282,11 @@ __attribute__((visibility("default"))) size_t dqp_al_newton_solve_bytes(const dq
 
 // What the two Newton loops share: the arguments of the candidates' line search and of the selection, the failure flag
 // cleared, the merit at the start
-static int newton_start(const AlProblem &v, const NewtonIo &o, const NewtonWork &w, LsAPX &Lc, SelP &Se)
+static int newton_start(const AlProblem &v, const NewtonIo &o, const NewtonWork &w, LsAP &Lc, SelP &Se)
 {
-    Lc = ls_args(v, o.xu, w.upd, w.merit, N_LINESEARCH);
+    Lc = ls_args(v, o.xu, w.upd, w.merit, AL_NCAND);
     Se.merit = w.merit; Se.upd = w.upd; Se.x0 = v.x0; Se.xu = o.xu; Se.merit_cur = w.merit_cur; Se.status = o.status;
-    Se.fail = o.fail; Se.info = w.info; Se.B = v.B; Se.n = v.n; Se.nz = v.nz(); Se.ncand = N_LINESEARCH;
+    Se.fail = o.fail; Se.info = w.info; Se.B = v.B; Se.n = v.n; Se.nz = v.nz(); Se.ncand = AL_NCAND;
     if (o.clear_fail && hipMemsetAsync(o.fail, 0, sizeof(int32_t), v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
     return launch_ls(ls_args(v, o.xu, w.upd, w.merit_cur, 0), v.stream);
 }
@@ -1415,7 +1299,7 @@ static int newton_banded(const AlProblem &v, const NewtonIo &o)
     if (v.too_large()) return DQP_ERR_TOO_LARGE;
     if (!o.L) return DQP_ERR_BAD_ARG;
     const NewtonWork w = newton_work(o.workspace, v.B, true, v.n, v.m, v.T);
-    LsAPX Lc;
+    LsAP Lc;
     SelP Se;
     int rc = newton_start(v, o, w, Lc, Se);
     if (rc) return rc;
@@ -1435,7 +1319,7 @@ static int newton_banded(const AlProblem &v, const NewtonIo &o)
 static int newton_dense(const AlProblem &v, const NewtonIo &o)
 {
     if (!v.model_ok()) return DQP_ERR_BAD_ARG;
-    if (v.n > 8 || v.m > 2) return DQP_ERR_TOO_LARGE;
+    if (v.n > LIN_NX || v.m > LIN_NU) return DQP_ERR_TOO_LARGE;
     const dqp_al_dims ad = {v.B, v.nz(), (int)v.ncon(), 0};
     AlP A = {};
     size_t lds = 0;
@@ -1443,11 +1327,11 @@ static int newton_dense(const AlProblem &v, const NewtonIo &o)
     if (rc) return rc;
     const NewtonWork w = newton_work(o.workspace, v.B, false, v.n, v.m, v.T);
     A.Jc = w.Jc; A.Qd = v.Qd; A.rho = v.rho; A.grad = w.grad; A.update = w.upd; A.L = o.L; A.info = w.info;
-    LsAPX Lc;
+    LsAP Lc;
     SelP Se;
     if ((rc = newton_start(v, o, w, Lc, Se)) != DQP_OK) return rc;
     // the clamped box rows carry the bound layout; the dense assembly and factorisation read them
-    LinPS Li = {};
+    LinP Li = {};
     Li.xu = o.xu; Li.x0 = v.x0; Li.ul = v.u.lower; Li.uu = v.u.upper; Li.Jx = w.Jx; Li.Ju = w.Ju; Li.resc = w.resc;
     Li.dt = v.dt; Li.B = v.B; Li.n = v.n; Li.m = v.m; Li.T = v.T; Li.dyn = v.model; Li.bsb = v.u.stride_b; Li.bst = v.u.stride_t;
     const dim3 lin_grid((unsigned)(((long long)v.B * v.T + 255) / 256));
@@ -1456,7 +1340,7 @@ static int newton_dense(const AlProblem &v, const NewtonIo &o)
     As.B = v.B; As.n = v.n; As.m = v.m; As.T = v.T; As.Qd = v.Qd; As.q = v.q; As.xu = o.xu;
     for (int it = 0; it < o.n_steps; ++it) {
         if (v.strided()) DQP_LAUNCH(al_linearize_kernel<true>, lin_grid, dim3(256), 0, v.stream, Li);
-        else DQP_LAUNCH(al_linearize_kernel<false>, lin_grid, dim3(256), 0, v.stream, static_cast<const LinP &>(Li));
+        else DQP_LAUNCH(al_linearize_kernel<false>, lin_grid, dim3(256), 0, v.stream, Li);
         DQP_LAUNCH(al_assemble_kernel, dim3(v.B), dim3(256), 0, v.stream, As);
         if ((rc = launch_newton(A, lds, v.stream)) != DQP_OK) return rc;
         if ((rc = launch_ls(Lc, v.stream)) != DQP_OK) return rc;
@@ -1531,7 +1415,7 @@ dqp_al_outer_update_xbounds(const dqp_al_mpc_dims *d, int model, double dt, cons
 __attribute__((visibility("default"))) int32_t dqp_al_ncon_xbounds(const dqp_al_mpc_dims *d)
 {
     if (!d || d->n_state <= 0 || d->n_ctrl <= 0 || d->T <= 0) return 0;
-    return d->T * d->n_state + 2 * d->T * d->n_ctrl + 2 * d->T * d->n_state;
+    return AlRows{d->n_state, d->n_ctrl, d->T, true}.ncon();
 }
 
 // the workspace does not depend on the rows: that of the `_bounds` twins

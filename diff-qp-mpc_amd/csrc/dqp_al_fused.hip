@@ -29,8 +29,6 @@
 //
 // Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2, the integrator),
 // 2 <= T <= 32, fp64.  RexQuadrotor (12 + 4) stays on the multi-launch path.
-#include <type_traits>
-
 #include "dqp_al_banded_kernels.h"
 
 namespace {
@@ -42,14 +40,12 @@ struct FusedP {
     int32_t *fail;
     double dt;
     int B, T, al_iter, newton_steps, n_prev;
+    long long bsb, bst;         // bound layout (dqp_al_bounds.h), read by the StridedBounds<> instantiations only
 };
-// + the bound layout (dqp_al_bounds.h): the argument of the StridedBounds<> instantiations and what the host code carries;
-// the vector instantiations keep FusedP as their argument
-struct FusedPS : FusedP { long long bsb, bst; };
-template <class Map> using FusedArg = std::conditional_t<strided_bounds<Map>::value, FusedPS, FusedP>;
 
+using dqp::AlRows;
+using dqp::AL_NCAND;
 constexpr int FG = 8, FNG = 64 / FG;      // lanes per group, groups per wavefront
-constexpr int NCAND = 20;                 // line-search candidates 2^-k, k = 0 .. 19 (al_utils.py:503-527)
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -63,7 +59,7 @@ template <class Map> struct FusedLds {
     using C = BandCfg<Map>;
     static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
     static constexpr int JBK = NX * (NT + 1);         // per knot: NX rows of [J[j][0 .. nt-1], res_j]
-    __host__ __device__ static int ncon(int T) { return T * NX + 2 * T * NU; }
+    __host__ __device__ static int ncon(int T) { return AlRows{NX, NU, T, false}.ncon(); }
     // StridedBounds<>: + the problem's own bounds, upper (T, nu) then lower (T, nu), staged once at the start
     static constexpr bool SB = strided_bounds<Map>::value;
     __host__ __device__ static size_t doubles(int T)
@@ -73,7 +69,7 @@ template <class Map> struct FusedLds {
 };
 
 template <class Map>
-__global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
+__global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 {
     using C = BandCfg<Map>;
     using Gr = Grp<FG>;
@@ -82,7 +78,9 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
     static_assert(NT <= FG, "a knot must fit an 8-lane group");
     const int lane = threadIdx.x, r = lane & (FG - 1), grp = lane / FG;
     const long long b = blockIdx.x;
-    const int T = P.T, nz = T * NT, neq = T * NX, ncon = neq + 2 * T * NU;
+    const int T = P.T, nz = T * NT;
+    const AlRows R = {NX, NU, T, false};
+    const int ncon = R.ncon();
     const bool inT = r < NT;
     const int rr = inT ? r : 0, rx = r < NX ? r : 0, iu = (inT && r >= NX) ? r - NX : 0;
 
@@ -106,10 +104,13 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
     if constexpr (SB) {         // visible to every lane behind the barrier that closes the start phase
         for (int e = lane; e < T * NU; e += 64) {
             const int t = e / NU, i = e - t * NU;
-            s_uu[e] = P.uu[b * P.bsb + t * P.bst + i];
-            s_ul[e] = P.ul[b * P.bsb + t * P.bst + i];
+            const long long o = dqp::al_bound_at<true>(b, t, i, P.bsb, P.bst);
+            s_uu[e] = P.uu[o]; s_ul[e] = P.ul[o];
         }
     }
+    // the bounds of control i of knot t: staged (SB) or the vector's element
+    auto upper = [&](int t, int i) { if constexpr (SB) return s_uu[t * NU + i]; else return uuv[i]; };
+    auto lower = [&](int t, int i) { if constexpr (SB) return s_ul[t * NU + i]; else return ulv[i]; };
 
     // ---- start (al_start_kernel): xu = [x_init | u_init], cost_start, warm start of (lam, rho), history row 0
     double rho;
@@ -126,21 +127,12 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
         }
         const double cost0 = 0.5 * wave_sum(quad) + wave_sum(lin);       // al_utils.compute_cost, diagonal cost
         const double *lam = P.lam_in + b * (long long)ncon;
-        double scale = 1.0;
-        rho = P.rho_in[b];
-        if (P.n_prev > 0) {
-            int pick = P.n_prev - 1;                     // torch.max of an all-False column: index 0 = the newest
-            for (int k = P.n_prev - 1; k >= 0; --k)
-                if (P.prev_cost[(long long)k * P.B + b] < cost0) { pick = k; break; }
-            const double *lh = P.prev_lam + ((long long)pick * P.B + b) * ncon;
-            double nh = 0.0, nl = 0.0;
-            for (int e = lane; e < ncon; e += 64) { nh += lh[e] * lh[e]; nl += lam[e] * lam[e]; }
-            scale = sqrt(wave_sum(nh)) / sqrt(wave_sum(nl));
-            rho = P.prev_rho[(long long)pick * P.B + b];
-        }
+        const dqp::AlWarm w = dqp::al_warm_start(P.n_prev, P.B, b, ncon, cost0, P.prev_cost, P.prev_lam, P.prev_rho, lam,
+                                                 P.rho_in[b], lane, 64, [](double v) { return wave_sum(v); });
+        rho = w.rho;
         double *l0 = P.hist_lam + b * (long long)ncon;
         for (int e = lane; e < ncon; e += 64) {
-            const double v = P.n_prev > 0 ? lam[e] * scale : lam[e];
+            const double v = P.n_prev > 0 ? lam[e] * w.scale : lam[e];
             s_lam[e] = v; l0[e] = v;
         }
         if (lane == 0) { P.hist_cost[b] = cost0; P.hist_rho[b] = rho; }
@@ -160,16 +152,12 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
                 const double u = with_upd ? s_upd[t * NT + j] : 0.0;
                 z[j] = fma(step, u, s_xu[t * NT + j]);
                 if (j < NX && t == 0) z[j] = x0v[j < NX ? j : 0];
-                acc += (0.5 * s_Qd[t * NT + j] * z[j] + s_q[t * NT + j]) * z[j];
+                acc += dqp::al_cost_term(s_Qd[t * NT + j], s_q[t * NT + j], z[j]);
             }
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
-                const int row = neq + t * 2 * NU + i;
-                double vh, vl;
-                if constexpr (SB) { vh = z[NX + i] - s_uu[t * NU + i]; vl = s_ul[t * NU + i] - z[NX + i]; }
-                else { vh = z[NX + i] - uuv[i]; vl = ulv[i] - z[NX + i]; }
-                acc += s_lam[row] * vh + s_lam[row + NU] * vl +
-                       0.5 * rho * (fmax(vh, 0.0) * fmax(vh, 0.0) + fmax(vl, 0.0) * fmax(vl, 0.0));
+                const int row = R.ctrl(t) + i;
+                acc += dqp::al_pair_term(rho, s_lam[row], s_lam[row + NU], z[NX + i] - upper(t, i), lower(t, i) - z[NX + i]);
             }
             if (t < T - 1) {
                 Map::template step<double>(z, z + NX, P.dt, xn);
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
                 for (int j = 0; j < NX; ++j) {
                     const double u = with_upd ? s_upd[(t + 1) * NT + j] : 0.0;
                     const double res = fma(step, u, s_xu[(t + 1) * NT + j]) - xn[j];
-                    acc += (0.5 * rho * res + s_lam[t * NX + j]) * res;
+                    acc += dqp::al_eq_term(rho, s_lam[R.eq(t) + j], res);
                 }
             }
         }
@@ -209,7 +197,7 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
             int bad = 0;
 #pragma unroll
             for (int j = 0; j < NX; ++j) { Mprev[j] = 0.0; mu_prev[j] = 0.0; }
-            const double lam_first = s_lam[(T - 1) * NX + rx];
+            const double lam_first = s_lam[R.eq(T - 1) + rx];
             for (int t = 0; t < T; ++t) {
                 const bool dynrow = t < T - 1;
                 const int tj = dynrow ? t : 0;
@@ -218,10 +206,10 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
                 for (int j = 0; j < NX; ++j) {
                     const double col = s_jb[tj * JBK + j * (NT + 1) + rr], res = s_jb[tj * JBK + j * (NT + 1) + NT];
                     Jc[j] = (dynrow && inT) ? col : 0.0;
-                    mu[j] = dynrow ? s_lam[tj * NX + j] + rho * res : 0.0;
+                    mu[j] = dynrow ? s_lam[R.eq(tj) + j] + rho * res : 0.0;
                 }
                 const double zr = s_xu[t * NT + rr], qdr = s_Qd[t * NT + rr], qr = s_q[t * NT + rr];
-                const int row = neq + t * 2 * NU + iu;
+                const int row = R.ctrl(t) + iu;
                 const double lup = s_lam[row], llo = s_lam[row + NU];
                 // gradient element r of this knot, and the diagonal terms of H_tt
                 double g = qdr * zr + qr, dg = qdr;
@@ -333,28 +321,21 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
                 for (int e = lane; e < T * NT * ROW; e += 64) fo[e] = s_fac[e];
             }
             // ---- line search: candidate k on group k % 8 (the surplus candidates of the last round are discarded)
-            for (int k0 = 0; k0 < NCAND; k0 += FNG) {
+            for (int k0 = 0; k0 < AL_NCAND; k0 += FNG) {
                 const int k = k0 + grp;
-                const double acc = merit_at((double)exp2f(-(float)k), true);       // float steps, as the reference
-                if (r == 0 && k < NCAND) s_merit[k] = acc;
+                const double acc = merit_at(dqp::al_step(k), true);
+                if (r == 0 && k < AL_NCAND) s_merit[k] = acc;
             }
             __syncthreads();
-            // torch.min over the candidates (NaN wins, else the first minimum), acceptance, update of the iterate
+            // the best candidate (al_select_kernel), acceptance, update of the iterate
             {
-                const bool has = lane < NCAND;
-                const double v = has ? s_merit[lane] : INFINITY;
-                const unsigned long long nanmask = __builtin_amdgcn_ballot_w64(has && v != v);
-                double mn = (v != v) ? INFINITY : v;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_xor(mn, off, 64));
-                const unsigned long long eq = __builtin_amdgcn_ballot_w64(has && v == mn);
-                const int arg = nanmask ? (int)__builtin_ctzll(nanmask) : (eq ? (int)__builtin_ctzll(eq) : 0);
-                const double best = __shfl(v, arg, 64);
-                const bool take = best < merit_cur;
-                merit_cur = best;                                   // new_merit regardless of acceptance
+                const bool has = lane < AL_NCAND;
+                const dqp::AlBest best = dqp::al_wave_argmin(has ? s_merit[lane] : INFINITY, has);
+                const bool take = best.merit < merit_cur;
+                merit_cur = best.merit;                             // new_merit regardless of acceptance
                 take_last = take ? 1.0 : 0.0;
                 if (take) {
-                    const double sb = (double)exp2f(-(float)arg);
+                    const double sb = dqp::al_step(best.arg);
                     for (int e = lane; e < nz; e += 64) s_xu[e] = e < NX ? P.x0[b * NX + e] : fma(sb, s_upd[e], s_xu[e]);
                 }
             }
@@ -371,36 +352,33 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedArg<Map> P)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) z[j] = s_xu[t * NT + j];
 #pragma unroll
-                for (int j = 0; j < NT; ++j) cost += (0.5 * s_Qd[t * NT + j] * z[j] + s_q[t * NT + j]) * z[j];
+                for (int j = 0; j < NT; ++j) cost += dqp::al_cost_term(s_Qd[t * NT + j], s_q[t * NT + j], z[j]);
                 if (t < T - 1) {
                     Map::template step<double>(z, z + NX, P.dt, xn);
 #pragma unroll
                     for (int j = 0; j < NX; ++j) {
                         const double res = s_xu[(t + 1) * NT + j] - xn[j];
                         rn2 += res * res;
-                        const double v = s_lam[t * NX + j] + rho * res;
-                        s_lam[t * NX + j] = v; ln[t * NX + j] = v;
+                        const double v = s_lam[R.eq(t) + j] + rho * res;
+                        s_lam[R.eq(t) + j] = v; ln[R.eq(t) + j] = v;
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < NX; ++j) {
                         const double res = s_xu[j] - x0v[j];
                         rn2 += res * res;
-                        const double v = s_lam[(T - 1) * NX + j] + rho * res;
-                        s_lam[(T - 1) * NX + j] = v; ln[(T - 1) * NX + j] = v;
+                        const double v = s_lam[R.eq(t) + j] + rho * res;
+                        s_lam[R.eq(t) + j] = v; ln[R.eq(t) + j] = v;
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < NU; ++i) {
-                    const double u = z[NX + i];
-                    double hi, lo;
-                    if constexpr (SB) { hi = u - s_uu[t * NU + i]; lo = s_ul[t * NU + i] - u; }
-                    else { hi = u - uuv[i]; lo = ulv[i] - u; }
-                    const int row = neq + t * 2 * NU + i;
-                    rn2 += fmax(hi, 0.0) * fmax(hi, 0.0) + fmax(lo, 0.0) * fmax(lo, 0.0);
-                    const double vu = fmax(s_lam[row] + rho * hi, 0.0), vl = fmax(s_lam[row + NU] + rho * lo, 0.0);   // AL_mpc.py:300-301
-                    s_lam[row] = vu; ln[row] = vu;
-                    s_lam[row + NU] = vl; ln[row + NU] = vl;
+                    const int row = R.ctrl(t) + i;
+                    const dqp::AlPairUpdate u = dqp::al_pair_update(rho, s_lam[row], s_lam[row + NU], z[NX + i] - upper(t, i),
+                                                                    lower(t, i) - z[NX + i]);
+                    rn2 += u.sq;
+                    s_lam[row] = u.up; ln[row] = u.up;
+                    s_lam[row + NU] = u.lo; ln[row + NU] = u.lo;
                 }
             }
             cost = wave_sum(cost);
@@ -446,12 +424,12 @@ bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id, bool strided = false)
     return lds > 0 && lds + FUSED_STATIC_LDS <= FUSED_LDS_LIMIT;
 }
 
-template <class Model> int launch_fused(const FusedPS &P, size_t lds, hipStream_t st)
+template <class Model> int launch_fused(const FusedP &P, size_t lds, hipStream_t st)
 {
     if (P.bsb != 0 || P.bst != 0)
         DQP_LAUNCH(al_solve_fused_kernel<StridedBounds<Model>>, dim3((unsigned)P.B), dim3(64), lds, st, P);
     else
-        DQP_LAUNCH(al_solve_fused_kernel<Model>, dim3((unsigned)P.B), dim3(64), lds, st, static_cast<const FusedP &>(P));
+        DQP_LAUNCH(al_solve_fused_kernel<Model>, dim3((unsigned)P.B), dim3(64), lds, st, P);
     return dqp::launched();
 }
 
@@ -525,7 +503,7 @@ dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, i
     if (!fused_ok(d, dyn_id, v.strided())) return DQP_ERR_TOO_LARGE;
     // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
     if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
-    FusedPS P = {};
+    FusedP P = {};
     P.x_init = io.x_init; P.u_init = io.u_init; P.x0 = v.x0; P.Qd = v.Qd; P.q = v.q; P.ul = v.u.lower; P.uu = v.u.upper;
     P.lam_in = v.lam; P.rho_in = v.rho; P.prev_cost = io.prev_cost; P.prev_lam = io.prev_lam; P.prev_rho = io.prev_rho;
     P.xu = io.xu; P.hist_cost = io.hist_cost; P.hist_lam = io.hist_lam; P.hist_rho = io.hist_rho; P.res_norm = io.res_norm;

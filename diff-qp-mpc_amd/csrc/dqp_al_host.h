@@ -27,7 +27,7 @@ struct AlProblem {
     hipStream_t stream;
 
     int nz() const { return T * (n + m); }
-    long long ncon() const { return (long long)T * n + 2LL * T * m + (has_x ? 2LL * T * n : 0); }
+    long long ncon() const { return AlRowsT<long long>{n, m, T, has_x}.ncon(); }
     bool strided() const { return al_bounds_strided(&u); }
     bool model_ok() const { return dyn::model_matches(model, n, m); }
     // beyond the block-tridiagonal kernels (and al_ls / al_outer, which share their limit)
@@ -51,7 +51,7 @@ inline AlProblem al_problem(const dqp_al_mpc_dims *d, int model, double dt, cons
     return v;
 }
 
-// The members that every kernel argument with both boxes has under the same names (MeritPX, LsAPX, OutP, BandP): where
+// The members that every kernel argument with both boxes has under the same names (MeritP, LsAP, OutP, BandP): where
 // such a struct's maker starts
 template <class P> P boxed_args(const AlProblem &v)
 {

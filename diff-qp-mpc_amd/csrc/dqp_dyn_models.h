@@ -360,9 +360,8 @@ struct RexQuadrotor {
 // One row per model: (id of include/dqp.h, state-space map, KC).  KC is the number of forward-mode directions one pass
 // of the model's Jacobian carries (dqp_dyn.hip: jac_kernel, dqp_mpc_sqp.hip: linearize_kernel), chosen per model for
 // its register demand.  Every entry that takes a dyn_id reaches the model's type through visit() below, on the host and
-// in the kernels (dqp_pdipm.hip true_dyn_res, dqp_ric_kernels.h model_residuals).
-// Places that also enumerate the models, each with its own switch:
-//   dqp_al.hip al_linearize_kernel: its instruction stream changes when it goes through visit() (its default is a model);
+// in the kernels (dqp_pdipm.hip true_dyn_res, dqp_ric_kernels.h model_residuals, dqp_al.hip al_linearize_kernel).
+// The one place that also enumerates models, with its own switch:
 //   dqp_dyn.hip dqp_dyn_forward_dynamics / _derivatives: the three Robot<> inner models, not the maps of this list.
 #define DQP_DYN_MODEL_LIST(X)                 \
     X(DQP_DYN_PENDULUM1L, Robot<Pendulum1l>, 3)     \

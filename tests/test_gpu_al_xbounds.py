@@ -36,7 +36,7 @@ STEP_CASES = [("pendulum_euler", 5, 6, 8), ("pendulum_euler", 5, 6, 16), ("cartp
 MPC_CASES = [("pendulum_euler", 5, 6), ("cartpole2l", 5, 3), ("cartpole1l", 6, 3), ("rexquadrotor", 4, 3)]
 # half-width of the widest state box of the Newton-step inputs (states N(0, 0.5^2)): the box fades to 20 % along the
 # horizon, so that a sample has knots with an active state row and knots with none (asserted in the test)
-STEP_WIDTH = {"pendulum_euler": 1.2, "cartpole1l": 1.5, "cartpole2l": 1.6, "rexquadrotor": 2.0}
+STEP_WIDTH = {"pendulum_euler": 1.2, "cartpole1l": 1.5, "cartpole2l": 1.6, "rexquadrotor": 2.0, "integrator": 1.2}
 
 
 @pytest.fixture(autouse=True)

@@ -795,6 +795,8 @@ def newton_case(robot, T, B, box):
     from oracle import al_solve_oracle as aso
     n, m = xb.SIZES[robot]
     d, lo, hi, xl, xh = xb.step_data(robot, T, B, seed=7 * T + B)
+    if box == "vector":                     # the n_ctrl-vector form of the control box: sample 0's first knot
+        lo, hi = lo[0, 0].copy(), hi[0, 0].copy()
     lam = d["lam"] if box == "state" else np.ascontiguousarray(d["lam"][:, :T * n + 2 * T * m])
     step = xb.host_step(robot, 0.05)
     with (xo.extended(xl, xh) if box == "state" else contextlib.nullcontext()):
@@ -805,8 +807,11 @@ def newton_case(robot, T, B, box):
     return d, lam, lo, hi, xl, xh, x_est, status, rhs, sol
 
 
+# T = 33: the line search beyond the lane groups' horizons (al_ls_kernel), with the control box as a vector ("vector"),
+# per sample and knot ("control") and with a state box
 NEWTON_CASES = [(r, T, B, g, box, 1) for r, T, B, g in AL_CASES for box in ("control", "state")] + \
-               [("pendulum_euler", 5, 3, 0, "control", 0)]
+               [("pendulum_euler", 5, 3, 0, "control", 0), ("pendulum_euler", 5, 3, 0, "vector", 0)] + \
+               [("integrator", 33, 3, 0, box, 1) for box in ("vector", "control", "state")]
 
 
 @pytest.mark.parametrize("robot,T,B,group,box,banded", NEWTON_CASES)
@@ -820,7 +825,7 @@ def test_al_newton_solve_through_the_c_abi(env, robot, T, B, group, box, banded)
     from diff_qp_mpc_amd import al_utils
     from diff_qp_mpc_amd.dynamics import DeviceDynamics
     _lib, _, lib = env
-    dyn = DeviceDynamics(robot)
+    dyn = DeviceDynamics(robot, dt=0.05)            # newton_case's step
     n, m = dyn.n_state, dyn.n_ctrl
     nt, nz = n + m, T * (n + m)
     d, lam, lo, hi, xl, xh, x_est, status_ref, rhs, sol = newton_case(robot, T, B, box)
@@ -871,8 +876,10 @@ def test_al_newton_solve_through_the_c_abi(env, robot, T, B, group, box, banded)
     assert nonzero_finite(np_(xu)) and nonzero_finite(np_(out))
     newton = [k for k in launches[0] if "al_banded_newton_kernel" in k]
     assert len(newton) == (4 if banded else 0), launches[0]
-    if banded:
-        assert all(("BoxBounds<" if box == "state" else "StridedBounds<") in k for k in newton), newton
+    family = {"state": "BoxBounds<", "control": "StridedBounds<", "vector": None}[box]
+    reads_bounds = newton + [k for k in launches[0] if "al_ls_kernel<" in k or "al_ls_group_kernel<" in k]
+    assert all((family in k) if family else ("Bounds<" not in k) for k in reads_bounds), reads_bounds
+    assert any("al_ls_kernel<" in k for k in launches[0]) == (T > 32), launches[0]
     assert wsb in sizes and fb in sizes, (wsb, fb, sizes)
 
 
