@@ -14,12 +14,13 @@ State bounds (`x_lower` / `x_upper`, both or neither; finite; (n,), (T, n), (B, 
 [x_t - x_upper, x_lower - x_t] of every knot, appended behind the control rows -- the multipliers then have
 T n + 2 T m + 2 T n columns.  A registered device model (n_state + n_ctrl <= 16, n_state <= 12, fp64) runs them on the
 block-tridiagonal kernels (dqp_al_mpc_solve_xbounds, or per AL iteration dqp_al_newton_solve_xbounds +
-dqp_al_outer_update_xbounds; the backward is the one without them).  A caller's own dynamics module (dx, dx_jac) runs
+dqp_al_outer_update_xbounds; the backward is the one without them), and with PERSISTENT_SOLVE on, where the single-launch
+solve exists (n_state + n_ctrl <= 8, T <= 32), as one launch (dqp_al_mpc_solve_fused_xbounds).  A caller's own dynamics
+module (dx, dx_jac) runs
 them on the caller-linearised block-tridiagonal step at every compiled pair, the wide ones included
 (NewtonALBandedJac: dqp_al_banded_newton_step_jac_xbounds, the line search's merit by dqp_al_merit_xbounds; the outer
 update stays in torch, which needs the module anyway).  Everything else takes the general torch path with the state
-rows: the single-launch solve (PERSISTENT_SOLVE), the dense AL kernel route, and the LU fallback after a Cholesky
-failure.
+rows: the dense AL kernel route and the LU fallback after a Cholesky failure.
 """
 import torch
 from torch.nn import Module

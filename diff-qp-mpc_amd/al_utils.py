@@ -650,8 +650,8 @@ class ALSolveDevice(torch.autograd.Function):
     (K,B,ncon), rho (K,B)), |res_clamp| (B) and the per-AL-iteration Cholesky-failure flags (int32).
     `fused`: the single-launch entry dqp_al_mpc_solve_fused (small batches; fused_solve_supported says where it
     exists) instead of the launch train -- the same arguments, outputs and backward.
-    `x_lower` / `x_upper`: state bounds (dqp_al_mpc_solve_xbounds; the launch train only): lam, the history rows and
-    `prev` then have dqp_al_ncon_xbounds columns.  Enqueue-only like the call without them."""
+    `x_lower` / `x_upper`: state bounds (dqp_al_mpc_solve_xbounds, with `fused` dqp_al_mpc_solve_fused_xbounds): lam, the
+    history rows and `prev` then have dqp_al_ncon_xbounds columns.  Enqueue-only like the call without them."""
 
     @staticmethod
     def forward(ctx, x_init, u_init, x0, Q, q, lam, rho, dyn, u_lower, u_upper, al_iter, prev, fused=False,
@@ -676,10 +676,11 @@ class ALSolveDevice(torch.autograd.Function):
         fail = torch.empty(al_iter, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.dqp_al_mpc_solve_bytes(ctypes.byref(dims))) // 8, **kw)
         if x_lower is not None:
-            assert not fused and ncon == T * n + 2 * T * m + 2 * T * n
+            assert ncon == T * n + 2 * T * m + 2 * T * n
             xbd = bounds_layout(x_lower, x_upper, B, T, n)
-            _lib.call("dqp_al_mpc_solve_xbounds", dev, dims, dyn.id, dyn.dt, al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(),
-                      xbd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn, L, status, fail, ws)
+            _lib.call("dqp_al_mpc_solve_fused_xbounds" if fused else "dqp_al_mpc_solve_xbounds", dev, dims, dyn.id, dyn.dt,
+                      al_iter, MAX_NEWTON_STEPS, *keep, bd.ref(), xbd.ref(), *keep2, pc, pl, pr, n_prev, xu, hc, hl, hr, resn,
+                      L, status, fail, ws)
         else:
             assert ncon == T * n + 2 * T * m
             _lib.call("dqp_al_mpc_solve_fused_bounds" if fused else "dqp_al_mpc_solve_bounds", dev, dims, dyn.id, dyn.dt,
@@ -700,10 +701,14 @@ class ALSolveDevice(torch.autograd.Function):
 def fused_solve_supported(n_batch, dyn, T, strided=False, state_bounds=False):
     """dqp_al_mpc_solve_fused exists for this registered model and horizon (n_state + n_ctrl <= 8, 2 <= T <= 32);
     `strided`: with per-sample / per-knot bounds, whose 2 T n_ctrl doubles are staged in LDS next to the problem.
-    `state_bounds`: False -- the single-launch solve has no state rows."""
-    if state_bounds:
-        return False
+    `state_bounds`: with a state box (dqp_al_mpc_solve_fused_xbounds), which stages both boxes and keeps the 2 T n_state
+    state rows of the multipliers in LDS too -- the answer for the largest carve, whatever the layouts of the boxes."""
     dims = _lib.dqp_al_mpc_dims(n_batch, dyn.n_state, dyn.n_ctrl, T)
+    if state_bounds:
+        n, m = dyn.n_state, dyn.n_ctrl
+        bd, xbd = _lib.dqp_al_bounds(None, None, T * m, m), _lib.dqp_al_bounds(None, None, T * n, n)
+        return bool(_lib.load().dqp_al_mpc_solve_fused_supported_xbounds(ctypes.byref(dims), dyn.id, ctypes.byref(bd),
+                                                                         ctypes.byref(xbd)))
     if strided:
         m = dyn.n_ctrl
         bd = _lib.dqp_al_bounds(None, None, T * m, m)

@@ -29,6 +29,12 @@
 //
 // Scope: registered models with n_state + n_ctrl <= 8 (the two pendulums, PendulumDx, cartpole-1, cartpole-2, the integrator),
 // 2 <= T <= 32, fp64.  RexQuadrotor (12 + 4) stays on the multi-launch path.
+//
+// State box (dqp_al_mpc_solve_fused_xbounds): the BoxBounds<Model> instantiations, one per model above.  Both boxes are
+// read through their strides and staged in LDS once at the start; lam and the history rows carry the 2 T n state rows
+// behind the control rows (AlRows::state).  A state pair enters the gradient and the diagonal of H_tt of its knot in
+// the sweep (lanes r < nx, at the iterate), the merit of the knot's owner (knot 0 at the pinned x0) and the outer
+// update of the knot's lane; the factor keeps its shape.  Everything it adds sits behind `if constexpr (XB)`.
 #include "dqp_al_banded_kernels.h"
 
 namespace {
@@ -41,6 +47,8 @@ struct FusedP {
     double dt;
     int B, T, al_iter, newton_steps, n_prev;
     long long bsb, bst;         // bound layout (dqp_al_bounds.h), read by the StridedBounds<> instantiations only
+    const double *xlo, *xhi;    // state box, read by the BoxBounds<> instantiations only (else NULL): lower / upper of
+    long long xsb, xst;         // (b, t, k) at [b xsb + t xst + k]; lam and the history rows then carry 2 T n more rows
 };
 
 using dqp::AlRows;
@@ -59,12 +67,15 @@ template <class Map> struct FusedLds {
     using C = BandCfg<Map>;
     static constexpr int NX = C::NX, NU = C::NU, NT = C::NT;
     static constexpr int JBK = NX * (NT + 1);         // per knot: NX rows of [J[j][0 .. nt-1], res_j]
-    __host__ __device__ static int ncon(int T) { return AlRows{NX, NU, T, false}.ncon(); }
+    // BoxBounds<>: + the 2 T nx state rows of lam and the problem's state bounds, upper (T, nx) then lower (T, nx)
+    static constexpr bool XB = box_bounds<Map>::value;
+    __host__ __device__ static int ncon(int T) { return AlRows{NX, NU, T, XB}.ncon(); }
     // StridedBounds<>: + the problem's own bounds, upper (T, nu) then lower (T, nu), staged once at the start
     static constexpr bool SB = strided_bounds<Map>::value;
     __host__ __device__ static size_t doubles(int T)
     {
-        return (size_t)5 * T * NT + ncon(T) + (size_t)T * JBK + (size_t)T * NT * C::ROW + 32 + (SB ? (size_t)2 * T * NU : 0);
+        return (size_t)5 * T * NT + ncon(T) + (size_t)T * JBK + (size_t)T * NT * C::ROW + 32 + (SB ? (size_t)2 * T * NU : 0) +
+               (XB ? (size_t)2 * T * NX : 0);
     }
 };
 
@@ -79,7 +90,8 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
     const int lane = threadIdx.x, r = lane & (FG - 1), grp = lane / FG;
     const long long b = blockIdx.x;
     const int T = P.T, nz = T * NT;
-    const AlRows R = {NX, NU, T, false};
+    constexpr bool XB = Lds::XB;
+    const AlRows R = {NX, NU, T, XB};
     const int ncon = R.ncon();
     const bool inT = r < NT;
     const int rr = inT ? r : 0, rx = r < NX ? r : 0, iu = (inT && r >= NX) ? r - NX : 0;
@@ -89,6 +101,7 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
     double *s_lam = s_q + nz, *s_jb = s_lam + ncon, *s_fac = s_jb + T * JBK, *s_merit = s_fac + T * NT * ROW;
     constexpr bool SB = Lds::SB;
     [[maybe_unused]] double *s_uu = s_merit + 32, *s_ul = s_uu + T * NU;       // SB only (FusedLds::doubles)
+    [[maybe_unused]] double *s_xhi = s_ul + T * NU, *s_xlo = s_xhi + T * NX;    // XB only
     // the group's tile for the transposed copies of the sweep (element (row, col) at [col TS + row])
     constexpr int TS = FG + 2, PS = FG * TS;
     __shared__ __attribute__((aligned(16))) double trs[FNG * PS];
@@ -106,6 +119,13 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
             const int t = e / NU, i = e - t * NU;
             const long long o = dqp::al_bound_at<true>(b, t, i, P.bsb, P.bst);
             s_uu[e] = P.uu[o]; s_ul[e] = P.ul[o];
+        }
+    }
+    if constexpr (XB) {
+        for (int e = lane; e < T * NX; e += 64) {
+            const int t = e / NX, j = e - t * NX;
+            const long long o = dqp::al_bound_at<true>(b, t, j, P.xsb, P.xst);
+            s_xhi[e] = P.xhi[o]; s_xlo[e] = P.xlo[o];
         }
     }
     // the bounds of control i of knot t: staged (SB) or the vector's element
@@ -158,6 +178,13 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
             for (int i = 0; i < NU; ++i) {
                 const int row = R.ctrl(t) + i;
                 acc += dqp::al_pair_term(rho, s_lam[row], s_lam[row + NU], z[NX + i] - upper(t, i), lower(t, i) - z[NX + i]);
+            }
+            if constexpr (XB) {         // the knot's state pairs (knot 0 at the pinned x0), read where they are used
+#pragma unroll
+                for (int j = 0; j < NX; ++j) {
+                    const int row = R.state(t) + j;
+                    acc += dqp::al_pair_term(rho, s_lam[row], s_lam[row + NX], z[j] - s_xhi[t * NX + j], s_xlo[t * NX + j] - z[j]);
+                }
             }
             if (t < T - 1) {
                 Map::template step<double>(z, z + NX, P.dt, xn);
@@ -226,6 +253,12 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
                     if (r < NX) {
                         g += (t > 0) ? prev : first;
                         dg += rho;
+                        if constexpr (XB) {     // the knot's state pair of element r, at the iterate (knot 0 too)
+                            const int xrow = R.state(t) + rx;
+                            const double xup = zr - s_xhi[t * NX + rx], xlw = s_xlo[t * NX + rx] - zr;
+                            g += (s_lam[xrow] + rho * fmax(xup, 0.0)) - (s_lam[xrow + NX] + rho * fmax(xlw, 0.0));
+                            dg += rho * ((xup > 0.0 ? 1.0 : 0.0) + (xlw > 0.0 ? 1.0 : 0.0));
+                        }
                     } else if (inT) {
                         g += (lup + rho * fmax(rup, 0.0)) - (llo + rho * fmax(rlo, 0.0));
                         dg += rho * ((rup > 0.0 ? 1.0 : 0.0) + (rlo > 0.0 ? 1.0 : 0.0));
@@ -380,6 +413,17 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
                     s_lam[row] = u.up; ln[row] = u.up;
                     s_lam[row + NU] = u.lo; ln[row + NU] = u.lo;
                 }
+                if constexpr (XB) {     // the knot's state rows: multipliers clamped at 0, their share of |res_clamp|
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        const int row = R.state(t) + j;
+                        const dqp::AlPairUpdate u = dqp::al_pair_update(rho, s_lam[row], s_lam[row + NX], z[j] - s_xhi[t * NX + j],
+                                                                        s_xlo[t * NX + j] - z[j]);
+                        rn2 += u.sq;
+                        s_lam[row] = u.up; ln[row] = u.up;
+                        s_lam[row + NX] = u.lo; ln[row + NX] = u.lo;
+                    }
+                }
             }
             cost = wave_sum(cost);
             rn2 = wave_sum(rn2);
@@ -401,36 +445,63 @@ __global__ __launch_bounds__(64) void al_solve_fused_kernel(FusedP P)
 constexpr size_t FUSED_STATIC_LDS = (size_t)FNG * FG * (FG + 2) * sizeof(double);
 constexpr size_t FUSED_LDS_LIMIT = 64 * 1024;
 
-// `strided`: the StridedBounds<> instantiation, whose carve also holds the problem's 2 T n_ctrl bounds
-template <class Map> size_t fused_lds_bytes(int T, bool strided)
+// `strided`: the StridedBounds<> instantiation, whose carve also holds the problem's 2 T n_ctrl bounds; `xbox`: the
+// BoxBounds<> one, which stages both boxes and holds the 2 T n_state state rows of lam
+template <class Map> size_t fused_lds_bytes(int T, bool strided, bool xbox)
 {
+    if (xbox) return FusedLds<BoxBounds<Map>>::doubles(T) * sizeof(double);
     return (strided ? FusedLds<StridedBounds<Map>>::doubles(T) : FusedLds<Map>::doubles(T)) * sizeof(double);
 }
 
-size_t fused_lds(int dyn_id, int T, bool strided = false)
+size_t fused_lds(int dyn_id, int T, bool strided = false, bool xbox = false)
 {
     return dqp::dyn::visit<size_t>(dyn_id, 0, [&](auto model) -> size_t {
         using Map = typename decltype(model)::Map;
-        if constexpr (Map::NX + Map::NU <= FG) return fused_lds_bytes<Map>(T, strided);
+        if constexpr (Map::NX + Map::NU <= FG) return fused_lds_bytes<Map>(T, strided, xbox);
         else return 0;          // the knot does not fit a group's tile
     });
 }
 
-bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id, bool strided = false)
+bool fused_ok(const dqp_al_mpc_dims *d, int dyn_id, bool strided = false, bool xbox = false)
 {
     if (!d || d->T < 2 || d->T > 32 || d->nbatch < 0) return false;
     if (!dqp::dyn::model_matches(dyn_id, d->n_state, d->n_ctrl) || d->n_state + d->n_ctrl > FG) return false;
-    const size_t lds = fused_lds(dyn_id, d->T, strided);
+    const size_t lds = fused_lds(dyn_id, d->T, strided, xbox);
     return lds > 0 && lds + FUSED_STATIC_LDS <= FUSED_LDS_LIMIT;
 }
 
 template <class Model> int launch_fused(const FusedP &P, size_t lds, hipStream_t st)
 {
-    if (P.bsb != 0 || P.bst != 0)
+    if (P.xlo)          // a state box: both boxes strided
+        DQP_LAUNCH(al_solve_fused_kernel<BoxBounds<Model>>, dim3((unsigned)P.B), dim3(64), lds, st, P);
+    else if (P.bsb != 0 || P.bst != 0)
         DQP_LAUNCH(al_solve_fused_kernel<StridedBounds<Model>>, dim3((unsigned)P.B), dim3(64), lds, st, P);
     else
         DQP_LAUNCH(al_solve_fused_kernel<Model>, dim3((unsigned)P.B), dim3(64), lds, st, P);
     return dqp::launched();
+}
+
+// Behind either front check (v.lam / v.rho: lam_in / rho_in): nbatch == 0, the buffers and the model, the kernel's limits
+int fused_solve(const dqp_al_mpc_dims *d, const dqp::AlProblem &v, const dqp::AlMpcIo &io)
+{
+    const int dyn_id = v.model;
+    if (const int r = v.ready(io.buffers_set() && v.model_ok()); r != 1) return r;
+    if (!fused_ok(d, dyn_id, v.strided(), v.has_x)) return DQP_ERR_TOO_LARGE;
+    // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
+    if (hipMemsetAsync(io.fail, 0, sizeof(int32_t) * (size_t)io.al_iter, v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
+    FusedP P = {};
+    P.x_init = io.x_init; P.u_init = io.u_init; P.x0 = v.x0; P.Qd = v.Qd; P.q = v.q; P.ul = v.u.lower; P.uu = v.u.upper;
+    P.lam_in = v.lam; P.rho_in = v.rho; P.prev_cost = io.prev_cost; P.prev_lam = io.prev_lam; P.prev_rho = io.prev_rho;
+    P.xu = io.xu; P.hist_cost = io.hist_cost; P.hist_lam = io.hist_lam; P.hist_rho = io.hist_rho; P.res_norm = io.res_norm;
+    P.fac = io.factor; P.status = io.status; P.fail = io.fail; P.bsb = v.u.stride_b; P.bst = v.u.stride_t;
+    P.xlo = v.x.lower; P.xhi = v.x.upper; P.xsb = v.x.stride_b; P.xst = v.x.stride_t;     // NULL / 0 without a state box
+    P.dt = v.dt; P.B = v.B; P.T = v.T; P.al_iter = io.al_iter; P.newton_steps = io.newton_steps; P.n_prev = io.n_prev;
+    const size_t lds = fused_lds(dyn_id, v.T, v.strided(), v.has_x);
+    return dqp::dyn::visit<int>(dyn_id, DQP_ERR_TOO_LARGE, [&](auto model) -> int {
+        using Map = typename decltype(model)::Map;
+        if constexpr (Map::NX + Map::NU <= FG) return launch_fused<Map>(P, lds, v.stream);
+        else return DQP_ERR_TOO_LARGE;
+    });
 }
 
 }  // namespace
@@ -498,23 +569,49 @@ dqp_al_mpc_solve_fused_bounds(const dqp_al_mpc_dims *d, int dyn_id, double dt, i
     const dqp::AlMpcIo io = {al_iter, newton_steps, x_init, u_init, prev_cost, prev_lam, prev_rho, n_prev,
                              xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, workspace};
     if (dqp::al_bounds_check(d, bounds) || !io.scalars_ok()) return DQP_ERR_BAD_ARG;
-    const dqp::AlProblem v = dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam_in, rho_in, bounds, nullptr, stream);
-    if (const int r = v.ready(io.buffers_set() && v.model_ok()); r != 1) return r;
-    if (!fused_ok(d, dyn_id, v.strided())) return DQP_ERR_TOO_LARGE;
-    // the flags are OR-ed into by every workgroup: cleared in front of the launch (a memset node under capture)
-    if (hipMemsetAsync(fail, 0, sizeof(int32_t) * (size_t)al_iter, v.stream) != hipSuccess) return DQP_ERR_LAUNCH;
-    FusedP P = {};
-    P.x_init = io.x_init; P.u_init = io.u_init; P.x0 = v.x0; P.Qd = v.Qd; P.q = v.q; P.ul = v.u.lower; P.uu = v.u.upper;
-    P.lam_in = v.lam; P.rho_in = v.rho; P.prev_cost = io.prev_cost; P.prev_lam = io.prev_lam; P.prev_rho = io.prev_rho;
-    P.xu = io.xu; P.hist_cost = io.hist_cost; P.hist_lam = io.hist_lam; P.hist_rho = io.hist_rho; P.res_norm = io.res_norm;
-    P.fac = io.factor; P.status = io.status; P.fail = io.fail; P.bsb = v.u.stride_b; P.bst = v.u.stride_t;
-    P.dt = v.dt; P.B = v.B; P.T = v.T; P.al_iter = io.al_iter; P.newton_steps = io.newton_steps; P.n_prev = io.n_prev;
-    const size_t lds = fused_lds(dyn_id, v.T, v.strided());
-    return dqp::dyn::visit<int>(dyn_id, DQP_ERR_TOO_LARGE, [&](auto model) -> int {
-        using Map = typename decltype(model)::Map;
-        if constexpr (Map::NX + Map::NU <= FG) return launch_fused<Map>(P, lds, v.stream);
-        else return DQP_ERR_TOO_LARGE;
-    });
+    return fused_solve(d, dqp::al_problem(d, dyn_id, dt, x0, Qdiag, q, lam_in, rho_in, bounds, nullptr, stream), io);
+}
+
+// State box (include/dqp.h): the BoxBounds<> instantiations, both boxes read through their strides.  `bounds` may be the
+// vector form; the carve is that of the strided call plus the 4 T n_state doubles of the state rows and bounds.
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_fused_supported_xbounds(const dqp_al_mpc_dims *d, int dyn_id, const dqp_al_bounds *bounds,
+                                         const dqp_al_bounds *xbounds)
+{
+    if (!d || d->n_state <= 0 || dqp::al_bounds_layout(bounds, d) != DQP_OK) return 0;
+    if (dqp::al_box_layout(xbounds, d, d->n_state) != DQP_OK) return 0;
+    return fused_ok(d, dyn_id, true, true) ? 1 : 0;
+}
+
+// that of dqp_al_mpc_solve_xbounds_bytes, so that one buffer serves both entries; the kernel does not write to it
+__attribute__((visibility("default"))) size_t dqp_al_mpc_solve_fused_bytes_xbounds(const dqp_al_mpc_dims *d)
+{
+    return dqp_al_mpc_solve_xbounds_bytes(d);
+}
+
+__attribute__((visibility("default"))) size_t
+dqp_al_mpc_solve_fused_lds_bytes_xbounds(const dqp_al_mpc_dims *d, int dyn_id, const dqp_al_bounds *bounds,
+                                         const dqp_al_bounds *xbounds)
+{
+    if (!dqp_al_mpc_solve_fused_supported_xbounds(d, dyn_id, bounds, xbounds)) return 0;
+    return fused_lds(dyn_id, d->T, true, true) + FUSED_STATIC_LDS;
+}
+
+__attribute__((visibility("default"))) int
+dqp_al_mpc_solve_fused_xbounds(const dqp_al_mpc_dims *d, int model, double dt, int32_t al_iter, int32_t newton_steps,
+                               const double *x_init, const double *u_init, const double *x0, const double *Qdiag,
+                               const double *q, const dqp_al_bounds *bounds, const dqp_al_bounds *xbounds,
+                               const double *lam_in, const double *rho_in, const double *prev_cost, const double *prev_lam,
+                               const double *prev_rho, int32_t n_prev, double *xu, double *hist_cost, double *hist_lam,
+                               double *hist_rho, double *res_norm, double *factor, double *status, int32_t *fail,
+                               void *workspace, void *stream)
+{
+    const dqp::AlMpcIo io = {al_iter, newton_steps, x_init, u_init, prev_cost, prev_lam, prev_rho, n_prev,
+                             xu, hist_cost, hist_lam, hist_rho, res_norm, factor, status, fail, workspace};
+    if (const int rc = dqp::al_xbounds_check(d, bounds, xbounds, d && dqp::dyn::model_matches(model, d->n_state, d->n_ctrl)))
+        return rc;
+    if (!io.scalars_ok()) return DQP_ERR_BAD_ARG;
+    return fused_solve(d, dqp::al_problem(d, model, dt, x0, Qdiag, q, lam_in, rho_in, bounds, xbounds, stream), io);
 }
 
 }  // extern "C"

@@ -39,7 +39,9 @@ extern "C" {
                            dqp_al_outer_update_xbounds, dqp_al_mpc_solve_xbounds (+ _bytes) -- state bounds on the
                            block-tridiagonal AL paths;
                            dqp_al_banded_newton_step_jac_xbounds, dqp_al_merit_xbounds -- state bounds on the
-                           caller-linearised block-tridiagonal step and in the merit kernel;)
+                           caller-linearised block-tridiagonal step and in the merit kernel;
+                           dqp_al_mpc_solve_fused_supported_xbounds / _bytes_xbounds / _lds_bytes_xbounds,
+                           dqp_al_mpc_solve_fused_xbounds -- state bounds on the single-launch solve;)
                            0.3.3: dqp_al_banded_newton_step_jac / dqp_al_banded_solve(dims, 0, ...) at 16 < n_state + n_ctrl <= 32
                            (compiled pairs), dqp_al_banded_jac_factor_bytes;
                            0.3.2: dqp_mpc_dims.n_state_host (padded stage-wise problems), dqp_mpc_qp_host_n_state;
@@ -750,6 +752,36 @@ int dqp_al_mpc_solve_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, 
                              const double *prev_rho, int32_t n_prev, double *xu, double *hist_cost, double *hist_lam,
                              double *hist_rho, double *res_norm, double *factor, double *status, int32_t *fail,
                              void *workspace, void *stream);
+
+/*
+ * dqp_al_mpc_solve_xbounds as ONE kernel launch (additive at 303; csrc/dqp_al_fused.hip): the argument list, the rows, the
+ * outputs and the kept factor of dqp_al_mpc_solve_xbounds, up to summation order, for the models and horizons of
+ * dqp_al_mpc_solve_fused (n_state + n_ctrl <= 8, 2 <= T <= 32).  Kernels: al_solve_fused_kernel<BoxBounds<Model>>, which
+ * reads both boxes through their strides (`bounds` may be the vector form) and stages them in LDS next to the problem.
+ * dqp_al_mpc_solve_fused_supported_xbounds: 1 where the entry exists and both layouts are in their tables, else 0; needs
+ * no device.  dqp_al_mpc_solve_fused_lds_bytes_xbounds: the launch's LDS -- that of dqp_al_mpc_solve_fused_lds_bytes at a
+ * strided `bounds` plus 4 T n_state doubles (the state rows of lam and the staged state bounds) --, 0 where
+ * _supported_xbounds is 0; at most 64 KB.  dqp_al_mpc_solve_fused_bytes_xbounds: the workspace size a caller passes, that
+ * of dqp_al_mpc_solve_xbounds_bytes, so that one buffer serves both entries.
+ * Return codes of dqp_al_mpc_solve_fused_xbounds: those of the `_xbounds` entries above in their order, then
+ * DQP_ERR_BAD_ARG for al_iter outside 1 .. 256, newton_steps < 1 or n_prev < 0, DQP_OK with nothing touched for
+ * nbatch == 0, DQP_ERR_BAD_ARG for a null buffer, and DQP_ERR_TOO_LARGE where _supported_xbounds is 0 (RexQuadrotor,
+ * T > 32: dqp_al_mpc_solve_xbounds serves them).  `fail` is cleared by a memset in front of the launch (a memset node
+ * under stream capture).  Only enqueues on `stream`.
+ */
+int dqp_al_mpc_solve_fused_supported_xbounds(const dqp_al_mpc_dims *dims, int model, const dqp_al_bounds *bounds,
+                                             const dqp_al_bounds *xbounds);
+size_t dqp_al_mpc_solve_fused_bytes_xbounds(const dqp_al_mpc_dims *dims);
+size_t dqp_al_mpc_solve_fused_lds_bytes_xbounds(const dqp_al_mpc_dims *dims, int model, const dqp_al_bounds *bounds,
+                                                const dqp_al_bounds *xbounds);
+int dqp_al_mpc_solve_fused_xbounds(const dqp_al_mpc_dims *dims, int model, double dt, int32_t al_iter,
+                                   int32_t newton_steps, const double *x_init, const double *u_init, const double *x0,
+                                   const double *Qdiag, const double *q, const dqp_al_bounds *bounds,
+                                   const dqp_al_bounds *xbounds, const double *lam_in, const double *rho_in,
+                                   const double *prev_cost, const double *prev_lam, const double *prev_rho,
+                                   int32_t n_prev, double *xu, double *hist_cost, double *hist_lam, double *hist_rho,
+                                   double *res_norm, double *factor, double *status, int32_t *fail, void *workspace,
+                                   void *stream);
 
 /*
  * State bounds for a dynamics the CALLER linearised (additive at 303): dqp_al_banded_newton_step_jac_bounds plus

@@ -7,7 +7,11 @@ variants alternate in blocks of `--block` calls; a block is timed with a host cl
 synchronise, the figure is the median over the blocks, with the quartiles as the spread.  A library trace of one
 forward per variant gives the launch count and the per-kernel device time.
 
-    python tools/bench_al_fused.py [--reps 30] [--block 20] [--out FILE.json]
+    python tools/bench_al_fused.py [--reps 30] [--block 20] [--state-box] [--shapes robot:T:B,...] [--out FILE.json]
+
+--state-box puts an active per-sample, per-knot state box (x_lower / x_upper) on every problem: the switch-off rows are
+then dqp_al_mpc_solve_xbounds and the switch-on rows dqp_al_mpc_solve_fused_xbounds; each row records how many samples
+end the traced call with a positive state multiplier.
 """
 import argparse
 import json
@@ -31,7 +35,7 @@ def dev(a):
     return torch.tensor(np.asarray(a), dtype=torch.float64, device="cuda")
 
 
-def setup(robot, T, B):
+def setup(robot, T, B, state_box=False):
     dyn = DeviceDynamics(robot)
     nx, nu = dyn.n_state, dyn.n_ctrl
     lim = 2.0 if robot == "pendulum_euler" else 250.0
@@ -43,10 +47,18 @@ def setup(robot, T, B):
     u_ref = torch.zeros(B, T, nu, dtype=torch.float64, device="cuda")
     C = torch.diag_embed(Qd).requires_grad_()
     c = (-(Qd * torch.cat([x_ref, u_ref], -1))).clone().requires_grad_()
+    box = {}
+    if state_box:
+        # around the reference line, 60 % of |x0| wide below and 18 % above at knot 1, narrowing along the horizon: knot 0
+        # (pinned to x0) stays inside, later knots are cut where the solution swings past the line
+        w = 0.6 * x0.abs().amax(1)[:, None, None] * torch.linspace(1.0, 0.25, T, dtype=torch.float64, device="cuda")[None, :, None]
+        w = (w + 0.02).expand(B, T, nx).clone()
+        w[:, 0] = x0.abs().amax(1)[:, None] + 0.05
+        box = dict(x_lower=(x_ref - w).contiguous(), x_upper=(x_ref + 0.3 * w).contiguous())
 
     def make():
         ctrl = AL_mpc.MPC(nx, nu, T, u_lower=lo, u_upper=hi, n_batch=B, verbose=0, solver_type="dense", dtype=torch.float64,
-                          eps=1e-5, exit_unconverged=False, backprop=False)
+                          eps=1e-5, exit_unconverged=False, backprop=False, **box)
         ctrl.mask = torch.ones(B, T, 1, device="cuda")
         return ctrl
     return dyn, make, x0, x_ref, u_ref, C, c
@@ -61,6 +73,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30, help="timed blocks per variant")
     ap.add_argument("--block", type=int, default=20, help="calls per timed block")
+    ap.add_argument("--state-box", action="store_true", help="an active (B, T, n) state box on every problem")
+    ap.add_argument("--shapes", default=None, help="robot:T:B,... instead of the built-in list")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -68,9 +82,13 @@ def main():
         clocks = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
     except Exception as e:      # noqa: BLE001
         clocks = "rocm-smi --showclocks: %r" % (e,)
-    result = {"device": torch.cuda.get_device_name(0), "clocks": clocks, "reps": args.reps, "block": args.block, "rows": []}
-    for robot, T, B in SHAPES:
-        dyn, make, x0, x_ref, u_ref, C, c = setup(robot, T, B)
+    result = {"device": torch.cuda.get_device_name(0), "clocks": clocks, "reps": args.reps, "block": args.block,
+              "state_box": args.state_box, "rows": []}
+    shapes = SHAPES
+    if args.shapes:
+        shapes = [(r, int(T), int(B)) for r, T, B in (s.split(":") for s in args.shapes.split(","))]
+    for robot, T, B in shapes:
+        dyn, make, x0, x_ref, u_ref, C, c = setup(robot, T, B, args.state_box)
         ctrl = make()
 
         def eager():
@@ -101,7 +119,11 @@ def main():
             key = "fused" if on else "multi"
             row[key + "_launches"] = len(tr.records)
             row[key + "_kernel_ms_sum"] = sum(ms for _, ms in tr.records)
-            row[key + "_kernels"] = {k.split("(")[0][-60:]: (n, round(ms, 5)) for k, (n, ms) in tr.by_kernel().items()}
+            short = lambda k: k.replace("(anonymous namespace)::", "").split("(")[0][-60:]
+            row[key + "_kernels"] = {short(k): (n, round(ms, 5)) for k, (n, ms) in tr.by_kernel().items()}
+            if args.state_box:
+                nu = dyn.n_ctrl
+                row[key + "_samples_with_active_state_rows"] = int((ctrl.lamda_prev[:, T * (dyn.n_state + 2 * nu):] > 0).any(1).sum())
         for mode in ("eager", "graph"):
             times = {False: [], True: []}
             for on in (False, True):            # warm-up of both variants
